@@ -30,10 +30,20 @@ One "step" = one pass of the hot path over one batch of synthetic objects:
   C3-train (the call lib/train.py:177-179 makes): 32 crops x 512 sub-sampled correspondences, RSLM(16,4,3) + LM 5,
       force_init_solve, with_pose_opt_plus + the loop's translation / rotation regularisers.
       C1 / C3 / C3-train are launch-bound: like C4 they are replayed from a hipGraph by default (`--launch auto`), and the
-      line carries the eagerly launched step time of the same run beside it (`eager`).
+      line carries the eagerly launched step time of the same run beside it (`eager`, with --full).
 fp32, inputs resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0).  `roofline` is the Jacobian sweep: the fused LM kernel credited one 28 B/point read per
+Prints ONE JSON line (rank 0).  A plain run sets up, spins up, warms up, times the K steps and prints the headline: `metric`,
+`value` (instances/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed step), the configuration and the rank
+evidence.  --dump-outputs DIR then writes what the last timed step computed (pose_opt, logw, cost_init, the loss, the
+gradients d/dx3d, d/dx2d, d/dw2d, ...) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: an array too large for
+its share holds a fixed, seeded sample of its flattened elements (`_dump_outputs`).  Inputs and sampling seeds are fixed, so
+two builds run with the same arguments can be compared output for output.
+
+--full adds everything else, each leg in a window of its own (the per-kernel one in front of the timed steps, the others after
+them): the per-kernel stage times (`kernel_ms`), the roofline legs, the same steps with stage events in the window, the
+eagerly launched step beside a replayed one (`eager`), the collective's checks and A/B (`collective`), the CPU baseline and
+the hipGraph replay of C2.  `roofline` is the Jacobian sweep: the fused LM kernel credited one 28 B/point read per
 logical sweep with its physical traffic beside it (`roofline.fused_lm`), and `roofline` itself =
 normal_equations_kernel, where one logical sweep IS one physical read of the correspondences, timed after the step loop
 IC-cold (launches rotate over distinct copies of the inputs, > 2 x the 256 MiB Infinity Cache).
@@ -94,6 +104,32 @@ def synth_problem(B, N, device, seed, dof=6, cam='pinhole800'):
 def _median(xs):
     xs = sorted(xs)
     return xs[len(xs) // 2]
+
+
+DUMP_BYTES = 64 * 2 ** 20       # --dump-outputs: all files together
+
+
+def _dump_outputs(out_dir, arrays, seed=0):
+    """`arrays`: name -> host tensor.  Writes out_dir/<name>.npy in float64 where the tensor is float64, float32 otherwise.
+    Every array gets an equal share of DUMP_BYTES; one larger than its share is replaced by a fixed, seeded sample of its
+    flattened elements (sorted unique indices drawn with numpy's default_rng(seed + position in name order)), so that the
+    same arguments always select the same elements.  Returns name -> {'shape', 'dtype', 'sampled'} for the log."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1) - 128                  # (the .npy header)
+    written = {}
+    for i, name in enumerate(sorted(arrays)):
+        t = arrays[name]
+        a = t.detach().cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        shape, flat = list(a.shape), a.reshape(-1)
+        cap = share // a.itemsize
+        sampled = flat.size > cap
+        if sampled:
+            idx = np.unique(np.random.default_rng(seed + i).integers(0, flat.size, size=cap))
+            flat = flat[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), flat if sampled else a)
+        written[name] = {'shape': shape, 'dtype': str(a.dtype), 'sampled': int(flat.size) if sampled else None}
+    return written
 
 
 def cpu_baseline(N, S, K, L, total_objects=1024, chunk=64, one_thread_objects=16):
@@ -399,6 +435,10 @@ def main(argv=None, device=None, backend='nccl'):
     ap.add_argument('--route', choices=['direct', 'c10d'], default='direct',
                     help="C4's collective: 'direct' = RCCL's ncclAllGather called on the step's own stream (sharding.RcclComm), "
                          "'c10d' = torch.distributed.all_gather_into_tensor -- to bisect a failing direct route from the command line")
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: per-kernel times, roofline legs, eager / A-B legs, CPU baseline, hipGraph replay')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)')
     args = ap.parse_args(argv)
     cfg = dict(CONFIGS[args.config])
     for k in ('objects', 'points', 'samples', 'amis_iters', 'lm_iters'):
@@ -452,6 +492,9 @@ def main(argv=None, device=None, backend='nccl'):
     from epropnp.levenberg_marquardt import LMSolver, RSLMSolver
     from epropnp.losses import MonteCarloPoseLoss, monte_carlo_pose_loss
 
+    # torch's global generator: the RSLM initialiser draws its Philox key from it (C1, C3-train, C4), so that the same
+    # arguments compute the same outputs in every run
+    torch.manual_seed(100 + rank)
     N, S, K, L, dof = cfg['points'], cfg['samples'], cfg['amis_iters'], cfg['lm_iters'], cfg['dof']
     caller = CALLER.get(args.config)
     strong = cfg['scaling'] == 'strong'
@@ -522,6 +565,15 @@ def main(argv=None, device=None, backend='nccl'):
     # no synchronisation), printed to stderr after the timed region -- tools/gpu_host_profile.sh
     seg = {} if os.environ.get('BENCH_HOST_SEGMENTS') == '1' else None
     seg_t = [0.0]
+    # --dump-outputs: detached views of what the latest step handed its caller (under a hipGraph: of the capture's static
+    # outputs, which every replay rewrites in place).  Detached: a kept grad_fn would keep the eager steps' AccumulateGrad
+    # nodes alive into the capture below (see `cost_fun.delta = None` there).
+    last = {} if args.dump_outputs else None
+
+    def keep(pose_opt, plus, logw, cost_init, loss):
+        outs = dict(pose_opt=pose_opt, logw=logw, cost_init=cost_init, loss=loss, grad_x3d=x3d.grad, grad_x2d=x2d.grad,
+                    grad_w2d=w2d.grad, pose_opt_plus=plus if with_plus else None)
+        last.update({k: v.detach() for k, v in outs.items() if v is not None})
 
     def mark(name):
         if seg is not None:
@@ -553,6 +605,8 @@ def main(argv=None, device=None, backend='nccl'):
             mark('loss')
             loss.backward()
             mark('backward')
+            if last is not None:
+                keep(pose_opt, plus, logw, cost_init, loss)
             return loss
         # Det step.  pose_opt is final here: its all-gather (with the rank's norm_factor input in the same payload) is issued
         # now, in stream order (sharding.ObjectExchange: why not a side stream); the loss takes the world mean out of the
@@ -575,6 +629,9 @@ def main(argv=None, device=None, backend='nccl'):
         mark('backward')
         gathered['pose_opt'] = exchange.objects()
         mark('exchange_objects')
+        if last is not None:
+            keep(pose_opt, plus, logw, cost_init, loss)
+            last['pose_opt_gathered'] = gathered['pose_opt'].detach()
         return loss
 
     def fence():
@@ -602,10 +659,12 @@ def main(argv=None, device=None, backend='nccl'):
     # box: 2.522 M instances/s with the events in the timed region, 2.605 M with them in front of it -- they used to disappear
     # in a 1.76 ms step; profiles/r04_bench_event_overhead.txt), they slow the host-bound eager Det step by 40 %, and they cannot
     # sit in a hipGraph at all.  BENCH_PROF_IN_REGION=1 puts them back into the timed region of an eager GPU-bound run.
-    prof_in_region = (launch == 'eager' and args.config not in LAUNCH_BOUND and os.environ.get('BENCH_PROF_IN_REGION', '0') == '1')
+    # (--full only: a plain run reports no per-kernel times and goes from the warm-up straight to the timed steps)
+    prof_in_region = (args.full and launch == 'eager' and args.config not in LAUNCH_BOUND
+                      and os.environ.get('BENCH_PROF_IN_REGION', '0') == '1')
     prof_steps = args.steps if prof_in_region else ((10 if args.config in LAUNCH_BOUND else 20) if on_gpu else 1)
     step_clocks = None
-    if not prof_in_region:
+    if args.full and not prof_in_region:
         fence()
         _hip.profile(enable=True, reset=True)
         if on_gpu and rank == 0:      # engine clock / power WHILE the step's kernels run (this window, not the timed one: the sampler is a host thread)
@@ -658,8 +717,11 @@ def main(argv=None, device=None, backend='nccl'):
     _hip.profile(enable=False)
     loss = held['loss']
     loss_val = float(loss.detach())
+    if last is not None and rank == 0:      # before any later leg launches the step again
+        written = _dump_outputs(args.dump_outputs, last)
+        print(json.dumps({'dumped_outputs': written, 'dir': args.dump_outputs}), file=sys.stderr)
     replay_check = None
-    if strong:      # what the LAST timed step fed the loss, against the same expression evaluated now, eagerly
+    if strong and args.full:      # what the LAST timed step fed the loss, against the same expression evaluated now, eagerly
         got, want = float(exchange.world_mean()), float(norm_factor_input())
         replay_check = {'norm_factor_input_last_step': got, 'evaluated_eagerly': want, 'norm_factor': float(loss_mod.norm_factor)}
         assert abs(got - want) <= 1e-5 * abs(want), ('the replayed step computed another norm_factor input', replay_check)
@@ -691,7 +753,7 @@ def main(argv=None, device=None, backend='nccl'):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt)
         assert ranks['rccl_world_size'] == world == int(ranks['all_reduce_of_ones']), ranks
-    if strong:
+    if strong and args.full:
         assert gathered['pose_opt'].shape[0] == total
         # the exchange only moves data: this rank's rows of the gathered tensor are its own pose outputs, bit for bit
         lo_, hi_ = sharding.shard_range(total, rank, world)
@@ -703,9 +765,9 @@ def main(argv=None, device=None, backend='nccl'):
     # headline can be compared like for like with BENCH_r01..r03 (~16 event records per step: ~3 % of a 1.5 ms step).
     STAGES = ('evaluate_cost', 'rslm_solve', 'lm_solve', 'amis_forward', 'amis_backward', 'adaptive_delta', 'mc_loss_forward',
               'mc_loss_backward', 'center_points', 'shift_poses')
-    stage_ms = {n: _hip.profile_read(n) for n in STAGES} if on_gpu else {}       # (read before the next leg re-uses the recorder)
+    stage_ms = {n: _hip.profile_read(n) for n in STAGES} if on_gpu and args.full else {}     # (read before the next leg re-uses the recorder)
     events_in_region = None
-    if on_gpu and launch == 'eager' and not prof_in_region and args.config not in LAUNCH_BOUND and world == 1:
+    if args.full and on_gpu and launch == 'eager' and not prof_in_region and args.config not in LAUNCH_BOUND and world == 1:
         n_ev = min(args.steps, 100)
         fence()
         _hip.profile(enable=True, reset=True)
@@ -719,7 +781,7 @@ def main(argv=None, device=None, backend='nccl'):
                             'steps': n_ev, 'note': 'per-stage HIP events recorded inside this window (the protocol of BENCH_r01..r03)'}
 
     eager_ms = None
-    if graph is not None:     # what a caller who just swaps the package gets: the same K steps launched eagerly, same run
+    if graph is not None and args.full:     # what a caller who just swaps the package gets: the same K steps launched eagerly, same run
         for _ in range(max(args.warmup, 3)):
             step()
         fence()
@@ -761,7 +823,7 @@ def main(argv=None, device=None, backend='nccl'):
         print(tp.key_averages().table(sort_by='self_cpu_time_total', row_limit=45, max_name_column_width=70), file=sys.stderr)
 
     ms_without = None
-    if strong:          # the collective's cost on the critical path, measured: the same steps without the exchange
+    if strong and args.full:        # the collective's cost on the critical path, measured: the same steps without the exchange
         exchange.disabled = True
         run = step
         if graph is not None:
@@ -789,13 +851,46 @@ def main(argv=None, device=None, backend='nccl'):
                'ms_per_step': round(ms, 4), 'scaling': cfg['scaling'], 'device': str(dev), 'loss': round(loss_val, 5),
                'config': {'name': args.config, 'objects_per_gpu': B, 'objects_total': total}}
         if strong:
-            out['collective'] = {'route': exchange.route, 'ms_per_step_without_exchange': round(ms_without, 4),
-                                 'bytes_per_rank': gathered_bytes,
-                                 'gathered_equals_local_bitwise': True, 'replayed_step_check': replay_check}
+            out['collective'] = {'route': exchange.route}
+            if args.full:
+                out['collective'].update(ms_per_step_without_exchange=round(ms_without, 4), bytes_per_rank=gathered_bytes,
+                                         gathered_equals_local_bitwise=True, replayed_step_check=replay_check)
         print(json.dumps(out), flush=True)
-    if rank == 0 and on_gpu:
+    if rank == 0 and on_gpu:        # the headline: all that a plain run measures and reports
         ms = elapsed / args.steps * 1e3
         value = total * args.steps / elapsed
+        names = {'C2': 'C2 batched synthetic', 'C5': 'C5 stress (one shard per GPU)', 'C4': 'C4 EPro-PnP-Det nuScenes shape',
+                 'C1': 'C1 demo/fit_identity.ipynb plumbing case', 'C3': 'C3 EPro-PnP-6DoF LineMOD shape, dense 64x64 crops',
+                 'C3-train': 'C3 EPro-PnP-6DoF LineMOD training call (512 sub-sampled correspondences)'}
+        par = (f'one batch of {total} objects split x{world} ({B} on rank 0), ONE all_gather_into_tensor (pose outputs + '
+               f'norm_factor) inside the step') if strong else f'objects sharded x{world}, no data-path collective'
+        out = {
+            'metric': f'PnP instances/sec (fwd+bwd, N={N} pts, {S} samples)',
+            'value': round(value, 1), 'unit': 'instances/s', 'n_gpus': world, 'ranks': ranks, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': round(ms, 4), 'higher_is_better': True, 'scaling': cfg['scaling'],
+            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'device_spinup_steps': SPINUP_STEPS,
+            # how the fp32 arithmetic is carried out where it is not plain fp32 instructions (DESIGN.md section 4, "Round 4")
+            'dtype_note': ('fp32 throughout; the pose x point projection of the two AMIS kernels is evaluated on v_mfma_f32_16x16x32_bf16 with each '
+                           'fp32 operand split into three bf16 pieces that sum to it exactly (8 of the 9 cross products carried, fp32 accumulation: '
+                           '1.4e-7 relative against 1.2e-7 for the fp32 MFMA); EPROPNP_FWD_PROJ=f32 EPROPNP_BWD_PROJ=f32 select the fp32 MFMA: '
+                           + ('fp32 MFMA selected' if os.environ.get('EPROPNP_FWD_PROJ', '')[:1] == 'f' and os.environ.get('EPROPNP_BWD_PROJ', '')[:1] == 'f'
+                              else 'split projection (default)')),
+            'launch': 'eager' if launch == 'eager' else 'hipGraph replay of the whole rank step, RCCL exchange included (captured once; fresh samples per replay)',
+            'launch_note': launch_note,
+            'config': {'workload': f'{names[args.config]}: {B} objects/GPU x N={N} points, S={S} MC samples, '
+                                   f'K={K} AMIS iters, L={L} LM iters, EProPnP{dof}DoF fwd+bwd'
+                                   + (', RSLM(16,64,3) init, normalize=True, Det loss' if args.config == 'C4' else '')
+                                   + ((f", RSLM{caller['rslm']} init" if caller['rslm'] else '') + (', per-object crop bounds' if caller['crop_bounds'] else '')
+                                      + f", z_min {caller['z_min']}, relative_delta {caller['relative_delta']}"
+                                      + (', with_pose_opt_plus + derivative regularisation' if caller['plus'] else '') if caller else ''),
+                       'name': args.config, 'objects_per_gpu': B, 'objects_total': total, 'num_points': N, 'mc_samples': S,
+                       'amis_iters': K, 'lm_iters': L, 'dof': dof, 'parallelism': par},
+            'loss': round(loss_val, 5),
+            'full': args.full,
+        }
+        if strong:
+            out['collective'] = {'backend': 'nccl (RCCL)' if dist is not None else 'none (single process)', 'route': exchange.route}
+    if rank == 0 and on_gpu and args.full:      # --full: the legs below run after the timed steps, each in a window of its own
         t_lm, t_fw, t_bw, t_ci = (stage_ms[n][0] for n in ('lm_solve', 'amis_forward', 'amis_backward', 'evaluate_cost'))
         assert stage_ms['lm_solve'][1] == prof_steps and stage_ms['amis_backward'][1] == prof_steps, stage_ms
         sweeps = 1 + L
@@ -813,9 +908,6 @@ def main(argv=None, device=None, backend='nccl'):
         ne_gbs = ne_bytes / (ne_mean_ms * 1e-3) / 1e9
         ne_clocks = LAST_SWEEP_CLOCKS[0]
         ne_traffic, ne_src = measured_traffic('normal_equations_kernel', shape_key) if shape_key else (None, None)
-        names = {'C2': 'C2 batched synthetic', 'C5': 'C5 stress (one shard per GPU)', 'C4': 'C4 EPro-PnP-Det nuScenes shape',
-                 'C1': 'C1 demo/fit_identity.ipynb plumbing case', 'C3': 'C3 EPro-PnP-6DoF LineMOD shape, dense 64x64 crops',
-                 'C3-train': 'C3 EPro-PnP-6DoF LineMOD training call (512 sub-sampled correspondences)'}
         ic_cold = ne_sets * ne_bytes >= 2 * IC_BYTES
         # roofline.large (default C2 line only): the same kernel on the C5-shard sweep, 470 MB per launch -- IC-cold by
         # construction and long enough (~0.1 ms) that launch ramp and tail do not set the figure
@@ -836,32 +928,10 @@ def main(argv=None, device=None, backend='nccl'):
                      'cache_state': f'IC-cold: {l_sets} copies x {l_bytes / 2 ** 20:.0f} MiB', 'traffic': l_traffic,
                      'traffic_source': l_src, 'clocks': LAST_SWEEP_CLOCKS[0]}
             del lp, lmk
-        par = (f'one batch of {total} objects split x{world} ({B} on rank 0), ONE all_gather_into_tensor (pose outputs + '
-               f'norm_factor) inside the step') if strong else f'objects sharded x{world}, no data-path collective'
-        out = {
-            'metric': f'PnP instances/sec (fwd+bwd, N={N} pts, {S} samples)',
-            'value': round(value, 1), 'unit': 'instances/s', 'n_gpus': world, 'ranks': ranks, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(ms, 4), 'higher_is_better': True, 'scaling': cfg['scaling'],
-            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'device_spinup_steps': SPINUP_STEPS,
-            # how the fp32 arithmetic is carried out where it is not plain fp32 instructions (DESIGN.md section 4, "Round 4")
-            'dtype_note': ('fp32 throughout; the pose x point projection of the two AMIS kernels is evaluated on v_mfma_f32_16x16x32_bf16 with each '
-                           'fp32 operand split into three bf16 pieces that sum to it exactly (8 of the 9 cross products carried, fp32 accumulation: '
-                           '1.4e-7 relative against 1.2e-7 for the fp32 MFMA); EPROPNP_FWD_PROJ=f32 EPROPNP_BWD_PROJ=f32 select the fp32 MFMA: '
-                           + ('fp32 MFMA selected' if os.environ.get('EPROPNP_FWD_PROJ', '')[:1] == 'f' and os.environ.get('EPROPNP_BWD_PROJ', '')[:1] == 'f'
-                              else 'split projection (default)')),
-            'launch': 'eager' if launch == 'eager' else 'hipGraph replay of the whole rank step, RCCL exchange included (captured once; fresh samples per replay)',
-            'launch_note': launch_note,
+        out.update({
             'kernel_ms_source': 'HIP events inside the library over the timed region' if prof_in_region else
                                 (f'HIP events inside the library over {prof_steps} eager steps BEFORE the timed region -- a separate window, and every event pair '
                                  f'adds ~2.5 us to its stage: the sum of kernel_ms may exceed ms_per_step by ~1 %'),
-            'config': {'workload': f'{names[args.config]}: {B} objects/GPU x N={N} points, S={S} MC samples, '
-                                   f'K={K} AMIS iters, L={L} LM iters, EProPnP{dof}DoF fwd+bwd'
-                                   + (', RSLM(16,64,3) init, normalize=True, Det loss' if args.config == 'C4' else '')
-                                   + ((f", RSLM{caller['rslm']} init" if caller['rslm'] else '') + (', per-object crop bounds' if caller['crop_bounds'] else '')
-                                      + f", z_min {caller['z_min']}, relative_delta {caller['relative_delta']}"
-                                      + (', with_pose_opt_plus + derivative regularisation' if caller['plus'] else '') if caller else ''),
-                       'name': args.config, 'objects_per_gpu': B, 'objects_total': total, 'num_points': N, 'mc_samples': S,
-                       'amis_iters': K, 'lm_iters': L, 'dof': dof, 'parallelism': par},
             # the Jacobian sweep against the HBM peak.  Headline = ONE physical sweep with the Infinity Cache out of the
             # picture; `fused_lm` = the LM kernel of the step, which reads the points once for its 1+L logical sweeps: its
             # physical fraction first, then SURVEY 8d's logical-sweep credit, named as such.
@@ -902,8 +972,7 @@ def main(argv=None, device=None, backend='nccl'):
             # engine / memory clock and package power sampled while the kernel_ms window ran (the sustained state the kernel times
             # were taken in: the AMIS kernels run close to the board's power cap, and boxes differ in where that puts the clock)
             'clocks_under_step_load': step_clocks,
-            'loss': round(loss_val, 5),
-        }
+        })
         if events_in_region is not None:
             out['with_stage_events_in_region'] = events_in_region
         if eager_ms is not None:
@@ -928,6 +997,7 @@ def main(argv=None, device=None, backend='nccl'):
             out['speedup_vs_cpu_baseline'] = round(value / out['cpu_baseline']['value'], 1)
         if world == 1 and not args.no_hipgraph and args.config == 'C2' and default_shape:
             out['hipgraph_replay'] = hipgraph_replay()      # informational: the same step replayed from a hipGraph
+    if rank == 0 and on_gpu:
         # RCCL writes its version banner through C stdio: into a pipe that is block-buffered and would land BEHIND this line at
         # exit -- push it out first, so that the JSON line is the last line of stdout
         try:

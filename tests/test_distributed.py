@@ -90,7 +90,7 @@ def test_shard_range_covers_everything():
             assert max(e[1] - e[0] for e in edges) - min(e[1] - e[0] for e in edges) <= 1
 
 
-def _bench_worker(rank, world, port, ret, config='C4', objects='9', stub=None):
+def _bench_worker(rank, world, port, ret, config='C4', objects='9', stub=None, extra=('--full',)):
     """bench.py's own main() as one of two gloo ranks: the emulation build is installed HERE, from the outside; bench.py gets
     a CPU device and the gloo backend through its test hook and skips only what needs the GPU (hipGraph, HIP events, roofline)."""
     import contextlib
@@ -105,7 +105,8 @@ def _bench_worker(rank, world, port, ret, config='C4', objects='9', stub=None):
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         rc = bench.main(['--gpus', str(world), '--config', config, '--objects', objects, '--points', '24', '--samples', '16', '--amis-iters', '2',
-                         '--lm-iters', '2', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-hipgraph'], device='cpu', backend='gloo')
+                         '--lm-iters', '2', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-hipgraph', *extra],
+                        device='cpu', backend='gloo')
     ret[rank] = (rc, buf.getvalue(), dist.is_initialized())
 
 
@@ -132,6 +133,34 @@ def test_bench_strong_scaling_step_two_gloo_ranks():
     assert c['bytes_per_rank'] == 9 * 4 * 4 + 4 and c['gathered_equals_local_bitwise'] is True and 'gloo' in c['route']
     chk = c['replayed_step_check']
     assert abs(chk['norm_factor_input_last_step'] - chk['evaluated_eagerly']) <= 1e-5 * abs(chk['evaluated_eagerly'])
+
+
+def test_bench_plain_line_and_dumped_outputs_two_gloo_ranks(tmp_path):
+    """A plain run (no --full) of the strong Det step with --dump-outputs: the headline line without the extra legs, and
+    rank 0's outputs of its last timed step on disk -- its own rows of pose_opt, the gathered batch, the gradients -- in
+    float32, the same files with the same values when the run is repeated."""
+    import json
+    import numpy as np
+    import conftest
+    conftest._emu_lib()
+    dumps = []
+    for i in range(2):
+        out = str(tmp_path / f'run{i}')
+        with mp.Manager() as mgr:
+            ret = mgr.dict()
+            mp.spawn(_bench_worker, args=(2, _free_port(), ret, 'C4', '9', None, ('--dump-outputs', out)), nprocs=2, join=True)
+            ret = dict(ret)
+        assert ret[0][0] == 0 and ret[1][0] == 0 and not ret[0][2] and not ret[1][2] and ret[1][1] == ''
+        line = json.loads([ln for ln in ret[0][1].splitlines() if ln.startswith('{')][-1])
+        assert line['steps'] == 2 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+        assert line['collective'] == {'route': line['collective']['route']}       # no A/B leg, no checks in a plain run
+        dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ['cost_init', 'grad_w2d', 'grad_x2d', 'grad_x3d', 'logw', 'loss', 'pose_opt', 'pose_opt_gathered']
+    assert a['pose_opt'].shape == (5, 4) and a['pose_opt_gathered'].shape == (9, 4) and a['grad_x3d'].shape == (5, 24, 3)
+    assert np.array_equal(a['pose_opt_gathered'][:5], a['pose_opt'])
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
 
 
 @pytest.mark.parametrize('config,objects', [('C4', '21'), ('C2', '2'), ('C5', '2')])
@@ -227,7 +256,7 @@ def test_bench_det_route_switch_and_clean_teardown(route):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(n), '--steps', '3', '--warmup', '1', '--config', 'C4',
-           '--route', route, '--no-cpu-baseline', '--no-hipgraph']
+           '--route', route, '--full', '--no-cpu-baseline', '--no-hipgraph']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     if r.returncode != 0:       # one retry for a rendezvous that did not come up (seen once on a box that took 75 s to receive the tree)
         sys.stderr.write('bench.py self-launch failed once, retrying:\n' + r.stderr[-1500:] + '\n')
@@ -252,7 +281,7 @@ def test_bench_reference_caller_configs(config):
     env = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--config', config, '--steps', '10', '--warmup', '2'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--config', config, '--steps', '10', '--warmup', '2', '--full'],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
@@ -281,7 +310,7 @@ def test_bench_multi_gpu_harness(config, form):
     n = 2 if torch.cuda.device_count() >= 2 else 1
     extra = {'C5': ['--objects', '512'], 'C2': ['--objects', '256'], 'C4': []}[config]     # slices keep the test short
     tail = [os.path.join(root, 'bench.py'), '--gpus', str(n), '--steps', '3', '--warmup', '1', '--config', config,
-            '--no-cpu-baseline', '--no-hipgraph'] + extra
+            '--full', '--no-cpu-baseline', '--no-hipgraph'] + extra
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
@@ -405,7 +434,7 @@ def test_real_rccl_world_of_one_under_device_masks(visible):
     if visible is not None:
         env['HIP_VISIBLE_DEVICES'] = visible
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--config', 'C4',
-           '--route', 'direct', '--no-cpu-baseline', '--no-hipgraph']
+           '--route', 'direct', '--full', '--no-cpu-baseline', '--no-hipgraph']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])

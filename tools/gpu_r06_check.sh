@@ -10,5 +10,5 @@ echo "# tools/bench_configs.py"; timeout 600 python tools/bench_configs.py 2>&1 
 } > $O/${TAG}_kernels.txt 2>&1
 cat $O/${TAG}_kernels.txt
 (timeout 900 python -m pytest tests/test_rslm.py tests/test_api_dropin.py tests/test_determinism_gpu.py tests/test_baseline_shapes_gpu.py tests/test_amis.py tests/test_erratum_gpu.py tests/test_graph_rng.py -m gpu -q -x 2>&1 | tail -6) > $O/${TAG}_pytest_subset.log; cat $O/${TAG}_pytest_subset.log
-(timeout 300 python bench.py 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench.json; python -c "
+(timeout 300 python bench.py --full 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench.json; python -c "
 import json; d=json.load(open('$O/${TAG}_bench.json')); print(d['value'], d['ms_per_step'], d['kernel_ms']); print(d['roofline']['frac'], d['roofline']['clocks']); print(d['roofline']['large']['frac'], d['roofline']['large']['clocks'])"

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Round-6 evidence run on the GPU box.  usage: tools/gpu_r06_evidence.sh [tag] [parts]   parts: any of t(ests) b(ench) p(mc) o(ther) c(onfigs + C5)
 TAG=${1:-r06}; PARTS=${2:-tbpoc}
+R=$PWD
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 O=/root/repo/gpurun_out
@@ -12,25 +13,25 @@ if [[ $PARTS == *t* ]]; then
   cat $O/${TAG}_smoke.log
 fi
 if [[ $PARTS == *b* ]]; then
-  (timeout 900 python bench.py 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench.json
+  (timeout 900 python bench.py --full 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench.json
   cut -c1-1800 $O/${TAG}_bench.json
   cd /tmp; rm -rf /tmp/prof
-  (timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench -- python /root/repo/bench.py --no-cpu-baseline --no-hipgraph 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_under_rocprof.json
+  (timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench -- python $R/bench.py --full --no-cpu-baseline --no-hipgraph 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_under_rocprof.json
   python /root/repo/tools/rocprof_summary.py /tmp/prof/bench_results.db | cut -c1-190 > $O/${TAG}_kernel_stats.txt
   head -14 $O/${TAG}_kernel_stats.txt
   cd /root/repo
   for c in C4 C5; do
-    (timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --config $c --steps 200 --warmup 5 --no-cpu-baseline 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_${c}_torchrun1.json
+    (timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --config $c --steps 200 --warmup 5 --full --no-cpu-baseline 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_${c}_torchrun1.json
     cut -c1-400 $O/${TAG}_bench_${c}_torchrun1.json; grep -o '"collective.*' $O/${TAG}_bench_${c}_torchrun1.json | cut -c1-600
   done
-  (timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --config C4 --launch eager --steps 200 --warmup 5 --no-cpu-baseline 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_C4_eager_torchrun1.json
+  (timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --config C4 --launch eager --steps 200 --warmup 5 --full --no-cpu-baseline 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_C4_eager_torchrun1.json
   cut -c1-300 $O/${TAG}_bench_C4_eager_torchrun1.json; grep -o '"collective.*' $O/${TAG}_bench_C4_eager_torchrun1.json | cut -c1-600
-  (BENCH_SELF_LAUNCH=1 timeout 600 python bench.py --gpus 1 --config C2 --steps 50 --warmup 5 --no-cpu-baseline --no-hipgraph 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_C2_selflaunch.json
+  (BENCH_SELF_LAUNCH=1 timeout 600 python bench.py --gpus 1 --config C2 --steps 50 --warmup 5 --full --no-cpu-baseline --no-hipgraph 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_C2_selflaunch.json
   cut -c1-700 $O/${TAG}_bench_C2_selflaunch.json
 fi
 if [[ $PARTS == *p* ]]; then
   cd /tmp
-  B="python /root/repo/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-hipgraph --no-large-sweep"      # every normal_equations_kernel dispatch has the C2 launch size
+  B="python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-hipgraph --no-large-sweep"      # every normal_equations_kernel dispatch has the C2 launch size
   i=0
   for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" \
              "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_INSTS_VALU_TRANS SQ_LDS_BANK_CONFLICT" \
@@ -53,13 +54,13 @@ fi
 if [[ $PARTS == *c* ]]; then
   # driver-reachable configs other than C2, and the C5 shard (8192 x 2048, IC-cold by construction): kernel trace + FETCH/WRITE
   for c in C1 C3 C3-train; do
-    (timeout 600 python bench.py --config $c --no-cpu-baseline 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_${c}.json
+    (timeout 600 python bench.py --config $c --full --no-cpu-baseline 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench_${c}.json
     cut -c1-500 $O/${TAG}_bench_${c}.json
   done
   bash tools/gpu_step_sequences.sh $TAG C1 C3 C3-train C4 > /dev/null 2>&1
   tail -1 $O/${TAG}_C4_step_sequence.txt
   cd /tmp
-  B="python /root/repo/bench.py --config C5 --steps 3 --warmup 1 --no-cpu-baseline --no-hipgraph"
+  B="python $R/bench.py --config C5 --steps 3 --warmup 1 --full --no-cpu-baseline --no-hipgraph"
   i=0
   for set in "FETCH_SIZE" "WRITE_SIZE"; do
     i=$((i+1)); rm -rf /tmp/pmc5_$i

@@ -14,5 +14,5 @@ for name, B, N, S, n in (('C2', 4096, 512, 512, $N2), ('C5-shard', 8192, 2048, 1
     print(f'{name}: 2 x {n} whole steps (forward + loss + backward), alone and beside a bf16 GEMM stream: every output and gradient bit-identical to the first launch ({time.time() - t0:.0f} s)')
 PY
 (timeout 2000 python -m pytest tests -m gpu -q 2>&1 | tail -3) | tee $O/${TAG}_pytest.log
-(timeout 400 python bench.py 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench.json; python -c "
+(timeout 400 python bench.py --full 2>&1 | grep "^{" | tail -1) > $O/${TAG}_bench.json; python -c "
 import json; d=json.load(open('$O/${TAG}_bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['large']['frac'])" | tee -a $O/${TAG}_soak.txt

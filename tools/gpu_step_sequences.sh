@@ -19,7 +19,7 @@ for c in $CFGS; do
   EAGER_IDX=-100
   if [ $c == C4 ]; then EAGER_IDX=$((-100 - W - STEPS)); fi      # C4 ends with W + STEPS replays of the step WITHOUT the exchange (A/B leg)
   if [ $c == C4 ]; then export RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517; else unset RANK LOCAL_RANK WORLD_SIZE; fi
-  (timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$c -o s -- python $R/bench.py --config $c --steps $STEPS --warmup $W --no-cpu-baseline 2>&1 | grep '^{' | tail -1) > $O/${TAG}_bench_${c}_under_rocprof.json
+  (timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$c -o s -- python $R/bench.py --config $c --steps $STEPS --warmup $W --full --no-cpu-baseline 2>&1 | grep '^{' | tail -1) > $O/${TAG}_bench_${c}_under_rocprof.json
   python $R/tools/rocprof_summary.py /tmp/prof_$c/s_results.db | cut -c1-200 > $O/${TAG}_${c}_kernel_stats.txt
   {
     echo "# $TAG: rocprofv3 kernel sequence of one REPLAYED step of \`bench.py --config $c\` (step $REPLAY_IDX of the run; tools/gpu_step_sequences.sh)."
