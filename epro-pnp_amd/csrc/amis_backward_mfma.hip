@@ -370,34 +370,41 @@ static int dispatch_bwd_npt(int npt, F&& f) {
   }
 }
 
-// returns 1 when the shape is not supported (caller falls back to amis_backward_kernel)
-int launch_amis_backward_mfma(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
-                              int mc_samples, const float* pose_init, const float* grad_cost_init, float* grad_x3d,
-                              float* grad_x2d, float* grad_w2d, float* grad_delta, int nsplit, hipStream_t st) {
-  const Problem d = to_device_problem(prob);
-  const int P = mc_samples + ((pose_init && grad_cost_init) ? 1 : 0);
+struct BwdPlan {
+  int waves, npt, P16, gw_rows;
+  size_t smem;
+  bool bf16;
+};
+
+// Which instantiation launch_amis_backward_mfma launches, and with what shape: a pure host function of the sizes, the tuning
+// variables and the CU count (launches nothing, reads no device memory), shared by the launcher below and by
+// epropnp_plan_amis_backward (c_api.hip) so that the two cannot drift.  Returns 1 when the shape is not supported (the
+// pose table does not fit LDS: the caller falls back to amis_backward_kernel).
+static int plan_amis_backward(const epropnp_problem* prob, int mc_samples, bool with_init, int nsplit, BwdPlan* out) {
+  const int B = prob->num_obj, N = prob->num_pts;
+  const int P = mc_samples + (with_init ? 1 : 0);
   const int P16 = ((P + 15) / 16) * 16 + 16;
   size_t smem = sizeof(float) * (15 * (size_t)P16 + 80 + kDropHistFloats);
   if (smem > 160 * 1024) return 1;
   // grad_w2d rows parked in LDS while the threshold's gradient is folded in (kernel comment): when the fold applies and the
   // rows fit next to three workgroups' pose tables per CU
   int gw_rows = 0;
-  if (prob->delta_stats != nullptr && nsplit == 1 && 3 * (smem + sizeof(float) * 2 * (size_t)d.N) <= 160 * 1024) {
-    gw_rows = d.N;
-    smem += sizeof(float) * 2 * (size_t)d.N;
+  if (prob->delta_stats != nullptr && nsplit == 1 && 3 * (smem + sizeof(float) * 2 * (size_t)N) <= 160 * 1024) {
+    gw_rows = N;
+    smem += sizeof(float) * 2 * (size_t)N;
   }
   // 4 waves x NPT <= 4 point tiles of 16 per chunk; larger N loops over chunks of 256 points against the LDS-resident pose table.
   // Measured at C2 in round 1: 4x4 (2 chunks) 1.07 ms, 4x8 1.11, 8x4 1.22.
   // Few objects (fewer than two waves per SIMD otherwise): 8 waves, one chunk of 512 points (B = 32 / 256: -7..9 %).
-  const int ptiles = (d.N + 15) / 16;
-  int waves = (d.B < 512 && ptiles > 16) ? 8 : 4, npt = 1;
+  const int ptiles = (N + 15) / 16;
+  int waves = (B < 512 && ptiles > 16) ? 8 : 4, npt = 1;
   while (npt < 4 && waves * npt < ptiles) npt *= 2;
   // Round 6, packed pair loop with pair accumulators (same-box A/Bs, profiles/r06_bwd_packed.txt): without a projection clamp 4 x 4
   // wins -- 784 ... 819 us at 206-248 VGPRs (two waves per SIMD) against 808 ... 838 us for 4 x 2 at 152 VGPRs (three): with two point-poses
   // per instruction the fewer instructions per pair of the four-tile loop (22.6 against 24.0) weigh more than the third wave.  With the
   // clamp the four-tile loop needs 218 VGPRs and two tiles win where the grid fills the chip: 913 against 945 us.  (The scalar loop of
   // round 5 preferred two tiles either way: 905 at 4 x 4, 868 at 4 x 2 with four waves.)  EPROPNP_TUNE=bwd_mfma=<waves>,<tiles> overrides.
-  if (has_bounds(prob) && waves == 4 && npt == 4 && d.B >= 2 * device_cu_count() && 3 * smem <= 160 * 1024) npt = 2;
+  if (has_bounds(prob) && waves == 4 && npt == 4 && B >= 2 * device_cu_count() && 3 * smem <= 160 * 1024) npt = 2;
   if (nsplit > 1) {      // 4 waves x the fewest tiles that still cover N with nsplit chunks in flight
     waves = 4; npt = 1;
     while (npt < 4 && waves * npt * nsplit < ptiles) npt *= 2;
@@ -409,9 +416,33 @@ int launch_amis_backward_mfma(const epropnp_problem* prob, const float* pose_sam
   // (With a projection clamp and four resident tiles the bf16 instantiation is a two-waves-per-SIMD kernel, see above.  It is taken
   // whatever the grid: which projection arithmetic an object gets must not depend on how many objects share the launch or on how
   // its points are split over workgroups -- the per-point gradients of the split and the unsplit launch are the same bits.)
-  const dim3 grid(padded_object_grid(d.B * nsplit)), block(64 * waves);
   bool bf16 = true;
   if (const char* e = getenv("EPROPNP_BWD_PROJ")) bf16 = (e[0] == 'f') ? false : (e[0] == 'b' ? true : bf16);
+  out->waves = waves; out->npt = npt; out->P16 = P16; out->gw_rows = gw_rows; out->smem = smem; out->bf16 = bf16;
+  return 0;
+}
+
+// epropnp_plan_amis_backward: {waves, tiles, bf16, rows parked in LDS, VALU fallback}; with the fallback the first four are zero
+int plan_amis_backward_record(const epropnp_problem* prob, int mc_samples, int with_init, int nsplit, int32_t* out) {
+  BwdPlan plan;
+  // (the split entry point never falls back: without an LDS pose table it fails, amis_kernels.hip)
+  const bool valu = (backward_valu_forced() && nsplit == 1) || plan_amis_backward(prob, mc_samples, with_init != 0, nsplit, &plan) != 0;
+  out[0] = valu ? 0 : plan.waves; out[1] = valu ? 0 : plan.npt; out[2] = valu ? 0 : plan.bf16; out[3] = valu ? 0 : plan.gw_rows > 0;
+  out[4] = valu;
+  return EPROPNP_OK;
+}
+
+// returns 1 when the shape is not supported (caller falls back to amis_backward_kernel)
+int launch_amis_backward_mfma(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
+                              int mc_samples, const float* pose_init, const float* grad_cost_init, float* grad_x3d,
+                              float* grad_x2d, float* grad_w2d, float* grad_delta, int nsplit, hipStream_t st) {
+  const Problem d = to_device_problem(prob);
+  BwdPlan plan;
+  if (plan_amis_backward(prob, mc_samples, pose_init && grad_cost_init, nsplit, &plan)) return 1;
+  const int waves = plan.waves, npt = plan.npt, P16 = plan.P16, gw_rows = plan.gw_rows;
+  const size_t smem = plan.smem;
+  const bool bf16 = plan.bf16;
+  const dim3 grid(padded_object_grid(d.B * nsplit)), block(64 * waves);
   dispatch_dof_bounds(prob->dof, has_bounds(prob), [&](auto DOF, auto BND) -> int {
     auto launch = [&](auto kern) -> int {
       allow_dynamic_lds((const void*)kern, smem);

@@ -452,16 +452,25 @@ unsigned long long amis_forward_split_bytes(const epropnp_problem* prob, int mc_
   return sizeof(float) * (unsigned long long)prob->num_obj * num_iter * g * s16;
 }
 
-int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_params* am, const float* pose_opt,
-                             const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
-                             float* proposals, hipStream_t st, const DenormOut* dn) {
-  const Problem d = to_device_problem(prob);
-  const int S = am->mc_samples, K = am->num_iter, s = S / K;
-  const int PL = prob->dof == 6 ? 7 : 4;
+struct FwdPlan {
   MfmaShape sh;
+  int waves, npt, G;      // npt == 0: the points stream through LDS
+  size_t smem;
+  bool bf16, spilled, truncated, chunked;      // truncated: a pose tile of the spill variant holds less than an iteration's samples
+};
+
+// Which instantiation launch_amis_forward_mfma launches for a problem, and with what shape: a pure host function of the sizes,
+// the tuning variables and the CU count (launches nothing, reads no device memory).  The launcher below calls it, and so does
+// epropnp_plan_amis_forward (c_api.hip) -- the tests' way of asserting WHICH kernel a case runs -- so the two cannot drift.
+// `scratch_bytes`: what the caller's split scratch holds (0: none).
+static int plan_amis_forward(const epropnp_problem* prob, int S, int K, unsigned long long scratch_bytes, FwdPlan* out) {
+  const int B = prob->num_obj, N = prob->num_pts;
+  const int s = S / K;
+  const int PL = prob->dof == 6 ? 7 : 4;
+  MfmaShape& sh = out->sh;
   sh.s16 = ((s + 15) / 16) * 16;
   // register mode: W waves x NPT point tiles of 16 cover N with the least padding (ties: prefer 4 waves)
-  const int ptiles = (d.N + 15) / 16;
+  const int ptiles = (N + 15) / 16;
   const int npt_opts[6] = {1, 2, 4, 8, 12, 16};
   int waves = 4, npt = 0, best = 1 << 30;
   for (int w : {4, 8, 2, 1}) {
@@ -475,10 +484,10 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
   // points through LDS instead (12 tiles were taken until round 5; EPROPNP_TUNE=fwd_mfma=4,12 still selects them)
   if (prob->dof == 4 && npt >= 12) npt = 0;
   // few objects (less than two waves per SIMD otherwise): spread an object over 8 waves (B = 32: 86 vs 93 us)
-  if (d.B < 512 && waves == 4 && npt == 8) { waves = 8; npt = 4; }
+  if (B < 512 && waves == 4 && npt == 8) { waves = 8; npt = 4; }
   { int ov[2]; if (tune_ints("fwd_mfma", ov, 2) && (ov[0] == 1 || ov[0] == 2 || ov[0] == 4 || ov[0] == 8) && (ov[1] == 0 || ov[1] == 1 || ov[1] == 2 || ov[1] == 4 || ov[1] == 8 || ov[1] == 12 || ov[1] == 16) && (ov[1] == 0 || ov[0] * ov[1] >= ptiles)) { waves = ov[0]; npt = ov[1]; } }
   if (npt == 0) {       // points stream through LDS in chunks; waves split the pose tiles
-    sh.chunk = ((d.N + 15) / 16) * 16;
+    sh.chunk = ((N + 15) / 16) * 16;
     if (sh.chunk > kChunk) sh.chunk = kChunk;
     if (best == (1 << 30)) waves = 4;
     const int tiles = sh.s16 / 16;
@@ -491,11 +500,11 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
   // points through LDS on 32 CUs -- but an eighth of them does.)
   int G = 1;
   {
-    const int g = forward_split_parts(d.B, ptiles);
-    const size_t need = sizeof(float) * (size_t)d.B * K * g * sh.s16;
+    const int g = forward_split_parts(B, ptiles);
+    const size_t need = sizeof(float) * (size_t)B * K * g * sh.s16;
     int ovf[1];
     const bool forced = env_ints("EPROPNP_FWD_SPLIT", ovf, 1);           // experiments: scratch from hipMallocAsync
-    if (g > 1 && (forced || (am->split_scratch != nullptr && am->split_scratch_bytes >= need))) {
+    if (g > 1 && (forced || (scratch_bytes != 0 && scratch_bytes >= need))) {
       int per_wave = (ptiles + 4 * g - 1) / (4 * g), o = 1;      // tiles per wave, rounded up to an instantiated NPT
       while (o < per_wave) o *= 2;
       if (o <= 8) { G = g; waves = 4; npt = o; sh.chunk = 0; }
@@ -512,14 +521,6 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
     sh.chunks = (ptiles + 31) / 32;
   }
   if (sh.chunks < 1) sh.chunks = 1;
-  AmisParams k;
-  k.S = S; k.K = K; k.WP = 1; k.eps = am->eps; k.mle_iter = am->acg_mle_iter; k.dispersion = am->acg_dispersion;
-  k.seed = am->seed; k.offset = am->offset; k.offset_dev = (const unsigned long long*)am->offset_dev; k.ablate = 0;
-  k.advance = (am->advance && am->advance_ticket && am->advance_count > 0) ? (unsigned long long*)am->advance : nullptr;
-  k.advance_ticket = (int*)am->advance_ticket; k.advance_count = am->advance_count;
-  k.split_timeout = split_timeout_cycles();
-  k.dn_offset = dn ? dn->offset : nullptr; k.dn_samples = dn ? dn->samples : nullptr; k.dn_pose_opt = dn ? dn->pose_opt : nullptr;
-  { int ab[1]; if (tune_ints("ablate", ab, 1)) k.ablate = ab[0]; }
   sh.ahead = 1;
   auto lds_bytes = [&](bool spilled) {
     return sizeof(float) * (12 * (size_t)sh.s16 + 8 * (size_t)sh.chunk + (spilled ? 0 : (((size_t)(PL + 3) * S + 3) & ~(size_t)3)) +
@@ -528,15 +529,17 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
                             ((s <= 64 * waves || !sh.ahead) ? 0 : 8 * (size_t)s));      // (s <= lanes: the noise shares the pose table)
   };
   size_t smem = lds_bytes(false);
-  float* spill = nullptr;
+  const int s16_full = sh.s16;
+  bool spilled = false;
   if (smem > 160 * 1024) {
+    spilled = true;
     // the sampler state does not fit LDS: stream the points (NPT = 0, 8 waves) and keep the per-sample arrays in a global
     // scratch buffer, allocated and released in stream order.  If one ITERATION's pose table (48 B per sample) and noise
     // buffer do not fit either, the noise is drawn inline and, if need be, the iteration's samples go through the table in
     // tiles (draw -> sweep -> costs to the scratch, per tile): no limit on mc_samples / num_iter (the reference has none,
     // epropnp.py:55-59)
     waves = 8; npt = 0; G = 1; sh.chunks = 1;
-    sh.chunk = ((d.N + 15) / 16) * 16;
+    sh.chunk = ((N + 15) / 16) * 16;
     if (sh.chunk > kChunk) sh.chunk = kChunk;
     const int tiles = sh.s16 / 16;
     while (waves > 1 && waves > tiles) waves /= 2;
@@ -549,16 +552,54 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
       if (sh.s16 < 16) return fail(EPROPNP_EINVAL, "amis_forward: no LDS left for a pose tile (%d points per chunk)", sh.chunk);
       smem = lds_bytes(true);
     }
-    if (hipMallocAsync((void**)&spill, sizeof(float) * (size_t)(PL + 3) * S * d.B, st) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(EPROPNP_ELAUNCH, "amis_forward: mc_samples %d needs a %zu B scratch buffer and hipMallocAsync failed "
-                  "(stream capture?)", S, sizeof(float) * (size_t)(PL + 3) * S * d.B);
-    }
   }
   // projection flavour (kernel comment): the bf16x3 split wherever the points are register-resident (C2 -9.8 %, 4096 x 1024 and the
   // C5 shard -16 %, profiles/r04_fwd_bf16_projection.txt); EPROPNP_FWD_PROJ=f32 keeps the fp32 MFMA
   bool bf16 = npt >= 1;
   if (const char* e = getenv("EPROPNP_FWD_PROJ")) bf16 = (e[0] == 'f') ? false : bf16;
+  out->waves = waves; out->npt = npt; out->G = G; out->smem = smem;
+  out->bf16 = bf16; out->spilled = spilled; out->truncated = sh.s16 < s16_full;
+  // (the knob: the chunked instantiation with one chunk)
+  out->chunked = !spilled && G == 1 && npt == 8 && (sh.chunks > 1 || (bf16 && tune_flag("fwd_chunked")));
+  return EPROPNP_OK;
+}
+
+// epropnp_plan_amis_forward: {waves, resident tiles, G, chunks, bf16, spilled, truncated, chunked instantiation}
+int plan_amis_forward_record(const epropnp_problem* prob, int S, int K, unsigned long long scratch_bytes, int32_t* out) {
+  FwdPlan plan;
+  if (int rc = plan_amis_forward(prob, S, K, scratch_bytes, &plan)) return rc;
+  out[0] = plan.waves; out[1] = plan.npt; out[2] = plan.G; out[3] = plan.sh.chunks; out[4] = plan.bf16; out[5] = plan.spilled;
+  out[6] = plan.truncated; out[7] = plan.chunked;
+  return EPROPNP_OK;
+}
+
+int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_params* am, const float* pose_opt,
+                             const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
+                             float* proposals, hipStream_t st, const DenormOut* dn) {
+  const Problem d = to_device_problem(prob);
+  const int S = am->mc_samples, K = am->num_iter;
+  const int PL = prob->dof == 6 ? 7 : 4;
+  FwdPlan plan;
+  if (int rc = plan_amis_forward(prob, S, K, am->split_scratch != nullptr ? am->split_scratch_bytes : 0, &plan)) return rc;
+  const MfmaShape sh = plan.sh;
+  const int waves = plan.waves, npt = plan.npt, G = plan.G;
+  const size_t smem = plan.smem;
+  const bool bf16 = plan.bf16;
+  AmisParams k;
+  k.S = S; k.K = K; k.WP = 1; k.eps = am->eps; k.mle_iter = am->acg_mle_iter; k.dispersion = am->acg_dispersion;
+  k.seed = am->seed; k.offset = am->offset; k.offset_dev = (const unsigned long long*)am->offset_dev; k.ablate = 0;
+  k.advance = (am->advance && am->advance_ticket && am->advance_count > 0) ? (unsigned long long*)am->advance : nullptr;
+  k.advance_ticket = (int*)am->advance_ticket; k.advance_count = am->advance_count;
+  k.split_timeout = split_timeout_cycles();
+  k.dn_offset = dn ? dn->offset : nullptr; k.dn_samples = dn ? dn->samples : nullptr; k.dn_pose_opt = dn ? dn->pose_opt : nullptr;
+  { int ab[1]; if (tune_ints("ablate", ab, 1)) k.ablate = ab[0]; }
+  float* spill = nullptr;
+  if (plan.spilled &&
+      hipMallocAsync((void**)&spill, sizeof(float) * (size_t)(PL + 3) * S * d.B, st) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(EPROPNP_ELAUNCH, "amis_forward: mc_samples %d needs a %zu B scratch buffer and hipMallocAsync failed "
+                "(stream capture?)", S, sizeof(float) * (size_t)(PL + 3) * S * d.B);
+  }
   const dim3 grid(padded_object_grid(d.B)), block(64 * waves);
   if (spill != nullptr) {
     dispatch_dof_bounds(prob->dof, has_bounds(prob), [&](auto DOF, auto BND) -> int {
@@ -625,7 +666,7 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
           return 0;
         };
         if constexpr (decltype(NPT)::value == 8) {
-          if (sh.chunks > 1 || (bf16 && tune_flag("fwd_chunked")))      // (the knob: the chunked instantiation with one chunk)
+          if (plan.chunked)
             return run(amis_forward_mfma_kernel<decltype(DOF)::value, decltype(BND)::value, 8, false, false, true, true>);
         }
         if constexpr (decltype(NPT)::value >= 1) {

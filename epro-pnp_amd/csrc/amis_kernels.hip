@@ -417,8 +417,7 @@ int launch_amis_backward(const epropnp_problem* prob, const float* pose_samples,
     return fail(EPROPNP_EINVAL, "amis_backward: NULL pointer");
   {   // projection on the matrix cores (amis_backward_mfma.hip) unless its LDS pose table does not fit;
       // EPROPNP_TUNE="bwd_impl=valu" forces this file's all-VALU kernel
-    const char* impl = tune_value("bwd_impl");
-    if (!(impl && impl[0] == 'v')) {
+    if (!backward_valu_forced()) {
       const int rc = launch_amis_backward_mfma(prob, pose_samples, grad_logweights, mc_samples, pose_init, grad_cost_init,
                                                grad_x3d, grad_x2d, grad_w2d, grad_delta, 1, st);
       if (rc <= 0) return rc;     // 1 = shape not supported there (pose table larger than LDS)

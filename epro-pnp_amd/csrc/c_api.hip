@@ -115,6 +115,42 @@ uint64_t epropnp_amis_forward_split_bytes(const epropnp_problem* prob, int32_t m
   return pnp::amis_forward_split_bytes(prob, mc_samples, num_iter);
 }
 
+// ---- launch plans: what the launchers would decide, from the same host functions; nothing is launched ----
+static int plan_args_ok(const epropnp_problem* prob, const int32_t* out, const char* what) {
+  if (int rc = pnp::check_plan_problem(prob)) return rc;
+  if (out == nullptr) return pnp::fail(EPROPNP_EINVAL, "%s: out is NULL", what);
+  return EPROPNP_OK;
+}
+
+int epropnp_plan_amis_forward(const epropnp_problem* prob, int32_t mc_samples, int32_t num_iter, int32_t has_scratch,
+                              int32_t num_cus, int32_t* out) {
+  if (int rc = plan_args_ok(prob, out, "plan_amis_forward")) return rc;
+  if (num_iter <= 0 || mc_samples <= 0 || mc_samples % num_iter != 0)
+    return pnp::fail(EPROPNP_EINVAL, "plan_amis_forward: mc_samples (%d) must be a positive multiple of num_iter (%d)", mc_samples, num_iter);
+  pnp::PlanCuScope cus(num_cus);
+  return pnp::plan_amis_forward_record(prob, mc_samples, num_iter, has_scratch ? ~0ull : 0ull, out);
+}
+
+int epropnp_plan_amis_backward(const epropnp_problem* prob, int32_t mc_samples, int32_t with_pose_init, int32_t num_split,
+                               int32_t num_cus, int32_t* out) {
+  if (int rc = plan_args_ok(prob, out, "plan_amis_backward")) return rc;
+  if (mc_samples < 0 || num_split < 1 || num_split > 16)
+    return pnp::fail(EPROPNP_EINVAL, "plan_amis_backward: mc_samples %d / num_split %d out of range", mc_samples, num_split);
+  pnp::PlanCuScope cus(num_cus);
+  return pnp::plan_amis_backward_record(prob, mc_samples, with_pose_init, num_split, out);
+}
+
+int epropnp_plan_evaluate_cost(const epropnp_problem* prob, int32_t num_cus, int32_t* out) {
+  if (int rc = plan_args_ok(prob, out, "plan_evaluate_cost")) return rc;
+  if (prob->num_pts > pnp::kMaxResidentPoints)
+    return pnp::fail(EPROPNP_EINVAL, "plan_evaluate_cost: num_pts %d exceeds the register-resident limit %d", prob->num_pts,
+                     pnp::kMaxResidentPoints);
+  pnp::PlanCuScope cus(num_cus);
+  const pnp::Shape s = pnp::cost_sweep_shape(prob->num_obj, prob->num_pts);
+  out[0] = s.waves; out[1] = s.ppl;
+  return EPROPNP_OK;
+}
+
 int epropnp_noise_stride(int dof) { return dof == 6 ? 8 : (dof == 4 ? 4 + 3 * 16 : -1); }
 
 int epropnp_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_params* par, const float* pose_init,

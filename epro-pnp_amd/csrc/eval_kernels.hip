@@ -1092,7 +1092,7 @@ int launch_evaluate_cost(const epropnp_problem* prob, const float* poses, int nu
     return fail(EPROPNP_EINVAL, "evaluate_cost: num_pts %d exceeds the register-resident limit %d", prob->num_pts,
                 kMaxResidentPoints);
   const Problem d = to_device_problem(prob);
-  const Shape s = choose_shape(d.B, d.N);
+  const Shape s = cost_sweep_shape(d.B, d.N);
   const dim3 grid(padded_object_grid(d.B)), block(64 * s.waves);
   dispatch_shape(prob->dof, s.ppl, has_bounds(prob), s.waves, [&](auto DOF, auto PPL, auto BND, auto MAXW) -> int {
     PNP_LAUNCH((evaluate_cost_kernel<decltype(DOF)::value, decltype(PPL)::value, decltype(BND)::value,

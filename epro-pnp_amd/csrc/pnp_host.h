@@ -39,6 +39,14 @@ inline int check_problem(const epropnp_problem* p) {
   return EPROPNP_OK;
 }
 
+// what the launch-plan queries read of a problem: sizes and dof (the device pointers may all be NULL)
+inline int check_plan_problem(const epropnp_problem* p) {
+  if (p == nullptr) return fail(EPROPNP_EINVAL, "problem is NULL");
+  if (p->dof != 4 && p->dof != 6) return fail(EPROPNP_EINVAL, "dof must be 4 or 6, got %d", p->dof);
+  if (p->num_obj <= 0 || p->num_pts <= 0) return fail(EPROPNP_EINVAL, "launch plan: num_obj and num_pts must be positive");
+  return EPROPNP_OK;
+}
+
 inline Problem to_device_problem(const epropnp_problem* p) {
   Problem d;
   d.x3d = p->x3d; d.x2d = p->x2d; d.w2d = p->w2d; d.cam = p->cam_mats;
@@ -124,10 +132,37 @@ inline const char* tune_value(const char* key) {
 inline bool tune_ints(const char* key, int* out, int n) { return parse_ints(tune_value(key), out, n); }
 inline bool tune_flag(const char* key) { return tune_value(key) != nullptr; }
 
+// The cost sweep (evaluate_cost): choose_shape with its defaults, or EPROPNP_TUNE="ev_shape=<waves>,<ppl>" -- the rule of ne_shape /
+// lm_shape, ignored when invalid -- with which a few objects reach the fat-lane instantiations that thousands of objects take.
+// Shared by the launcher and by epropnp_plan_evaluate_cost.
+inline Shape cost_sweep_shape(int B, int N) {
+  Shape s = choose_shape(B, N);
+  int ov[2];
+  if (tune_ints("ev_shape", ov, 2) && valid_shape_override(ov[0], ov[1], N)) { s.waves = ov[0]; s.ppl = ov[1]; }
+  return s;
+}
+
+// EPROPNP_TUNE="bwd_impl=valu": epropnp_amis_backward takes the all-VALU kernel (amis_kernels.hip) whatever the shape
+inline bool backward_valu_forced() {
+  const char* impl = tune_value("bwd_impl");
+  return impl && impl[0] == 'v';
+}
+
 // Compute units of the current device (hipDeviceAttributeMultiprocessorCount, cached): what the workgroup-split variants
 // size their grids against -- a partitioned (CPX) MI355X or another part reports its own count; the CPU emulation of the
 // tests is a "device" with ONE compute unit (it runs one workgroup at a time), which switches the splits off by default.
+// (The launch-plan queries -- epropnp_plan_*, c_api.hip -- can ask for the plan of another CU count: PlanCuScope.)
+inline int& plan_cu_override() {
+  static thread_local int cus = 0;
+  return cus;
+}
+struct PlanCuScope {
+  int prev;
+  explicit PlanCuScope(int cus) : prev(plan_cu_override()) { if (cus > 0) plan_cu_override() = cus; }
+  ~PlanCuScope() { plan_cu_override() = prev; }
+};
 inline int device_cu_count() {
+  if (plan_cu_override() > 0) return plan_cu_override();
   static int cached[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -183,6 +218,9 @@ int launch_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_par
                                float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
                                float* pose_samples, hipStream_t st);
 unsigned long long amis_forward_split_bytes(const epropnp_problem* prob, int mc_samples, int num_iter);
+// launch plans as int records (include/epropnp_hip.h: epropnp_plan_*): host only, nothing is launched
+int plan_amis_forward_record(const epropnp_problem* prob, int S, int K, unsigned long long scratch_bytes, int32_t* out);
+int plan_amis_backward_record(const epropnp_problem* prob, int mc_samples, int with_init, int nsplit, int32_t* out);
 int launch_evaluate_cost(const epropnp_problem* prob, const float* poses, int num_poses, float* cost, hipStream_t st);
 int launch_cost_pose_cam_grad(const epropnp_problem* prob, const float* poses, const float* weights, int num_poses,
                               int m_pose, float* out_m, float* out_gk, hipStream_t st);

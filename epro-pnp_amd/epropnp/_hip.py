@@ -64,7 +64,7 @@ class McParams(C.Structure):
                 ('rslm_scratch_bytes', C.c_uint64), ('lm_scratch', C.c_void_p), ('lm_scratch_bytes', C.c_uint64)]
 
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 _lib = None
 
 
@@ -76,6 +76,9 @@ def _declare(lib):
     lib.epropnp_profile_enable.argtypes = [C.c_int]
     lib.epropnp_amis_forward_split_bytes.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32]
     lib.epropnp_amis_forward_split_bytes.restype = C.c_uint64
+    lib.epropnp_plan_amis_forward.argtypes = [C.POINTER(Problem), i32, i32, i32, i32, C.POINTER(i32)]
+    lib.epropnp_plan_amis_backward.argtypes = [C.POINTER(Problem), i32, i32, i32, i32, C.POINTER(i32)]
+    lib.epropnp_plan_evaluate_cost.argtypes = [C.POINTER(Problem), i32, C.POINTER(i32)]
     lib.epropnp_async_status.argtypes = [C.POINTER(C.c_int32), C.c_int]
     lib.epropnp_async_status.restype = C.c_int
     lib.epropnp_async_status_word.restype = C.POINTER(C.c_int32)
@@ -115,7 +118,7 @@ def _declare(lib):
     for name in ('evaluate_cost', 'normal_equations', 'lm_solve', 'amis_forward', 'amis_backward', 'adaptive_delta',
                  'mc_loss_forward', 'mc_loss_backward', 'rslm_draw', 'gn_step_forward', 'gn_step_backward', 'rslm_solve', 'center_points', 'shift_poses', 'prepare_forward', 'prepare_backward', 'pose_opt_plus_forward', 'pose_opt_plus_backward', 'shift_poses_backward', 'prepare_dense_forward',
                  'prepare_dense_backward', 'amis_backward_split', 'monte_carlo_forward', 'cost_pose_cam_grad', 'mc_loss_reduce',
-                 'mc_loss_reduce_backward'):
+                 'mc_loss_reduce_backward', 'plan_amis_forward', 'plan_amis_backward', 'plan_evaluate_cost'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -130,7 +133,8 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_prepare_dense_forward', 'epropnp_prepare_dense_backward', 'epropnp_amis_backward_split',
            'epropnp_monte_carlo_forward', 'epropnp_cost_pose_cam_grad', 'epropnp_async_status',
            'epropnp_async_status_word', 'epropnp_amis_forward_split_bytes', 'epropnp_rslm_solve_scratch_bytes',
-           'epropnp_lm_solve_split_bytes', 'epropnp_mc_loss_reduce', 'epropnp_mc_loss_reduce_backward', 'epropnp_exchange_pack')
+           'epropnp_lm_solve_split_bytes', 'epropnp_mc_loss_reduce', 'epropnp_mc_loss_reduce_backward', 'epropnp_exchange_pack',
+           'epropnp_plan_amis_forward', 'epropnp_plan_amis_backward', 'epropnp_plan_evaluate_cost')
 
 
 def lib():

@@ -415,6 +415,62 @@ def backward_split(B, N, S):
     return n
 
 
+class PlanProblem:
+    """Sizes of a problem for `launch_plan`, without tensors: the plan of a shape that is not (or cannot be) allocated, such as
+    a full-size workload on a machine without a device.  The launch plans read num_obj, num_pts, dof and whether bounds / the
+    delta fold are present; the pointers that say "present" address a host dummy that is never dereferenced."""
+    _present = (C.c_float * 4)()
+
+    def __init__(self, B, N, dof, bounds=False, delta_fold=False):
+        self.B, self.N, self.dof = int(B), int(N), int(dof)
+        here = C.addressof(self._present)
+        self.c = _hip.Problem(None, None, None, None, here if bounds else None, here if bounds else None, None, 0.1,
+                              self.B, self.N, self.dof, 0.0, None, here if delta_fold else None, 0.0)
+
+
+_FWD_PLAN = ('waves', 'tiles', 'G', 'chunks', 'bf16', 'spilled', 'truncated', 'chunked')
+_BWD_PLAN = ('waves', 'tiles', 'bf16', 'parked', 'valu')
+
+
+def launch_plan(kind, prob, mc_samples=None, num_iter=None, pose_init=False, nsplit=None, scratch=None, cus=None):
+    """Which kernel instantiation a call on `prob` (a PnPProblem or a PlanProblem) would launch, as a dict; nothing is launched.
+    The library answers from the functions its launchers decide with (include/epropnp_hip.h: epropnp_plan_*), under the
+    environment as it is now (EPROPNP_TUNE, EPROPNP_FWD_SPLIT, ...).  `cus`: plan for a device of that many compute units
+    (None: the current device) -- the plan of a shape on a 256-CU MI355X can be computed anywhere.
+
+      'forward'  (amis_forward; mc_samples, num_iter; scratch: whether the split scratch is handed over, None = as amis_forward
+                 does) -> waves, tiles (resident point tiles per wave, 0 = the points stream through LDS), G (workgroups per
+                 object), chunks, bf16, spilled, truncated, chunked (the chunked instantiation is launched)
+      'backward' (amis_backward; mc_samples, pose_init: whether pose_init / grad_cost_init are given, nsplit: None = what
+                 backward_split decides) -> nsplit, waves, tiles, bf16, parked (grad_w2d rows in LDS for the delta fold), valu
+                 (the all-VALU kernel is taken: waves / tiles are 0)
+      'cost'     (evaluate_cost) -> waves, ppl (points per lane)"""
+    n_cus = 0 if cus is None else int(cus)
+    if kind == 'forward':
+        out = (C.c_int32 * 8)()
+        has = (prob.B <= 64) if scratch is None else bool(scratch)      # (split_scratch: none above 64 objects)
+        _hip.call('epropnp_plan_amis_forward', C.byref(prob.c), int(mc_samples), int(num_iter), int(has), n_cus, out)
+        plan = dict(zip(_FWD_PLAN, out))
+        for k in ('bf16', 'spilled', 'truncated', 'chunked'):
+            plan[k] = bool(plan[k])
+        return plan
+    if kind == 'backward':
+        out = (C.c_int32 * 5)()
+        S = int(mc_samples)
+        n = backward_split(prob.B, prob.N, S) if nsplit is None else int(nsplit)
+        _hip.call('epropnp_plan_amis_backward', C.byref(prob.c), S, int(bool(pose_init)), n, n_cus, out)
+        plan = dict(zip(_BWD_PLAN, out))
+        for k in ('bf16', 'parked', 'valu'):
+            plan[k] = bool(plan[k])
+        plan['nsplit'] = n
+        return plan
+    if kind == 'cost':
+        out = (C.c_int32 * 2)()
+        _hip.call('epropnp_plan_evaluate_cost', C.byref(prob.c), n_cus, out)
+        return {'waves': out[0], 'ppl': out[1]}
+    raise ValueError(f"launch_plan: kind must be 'forward', 'backward' or 'cost', got {kind!r}")
+
+
 def amis_backward(prob, pose_samples, grad_logweights, pose_init=None, grad_cost_init=None, nsplit=None, cstruct=None):
     """-> grad_x3d (B,N,3), grad_x2d (B,N,2), grad_w2d (B,N,2), grad_delta (B,).
     `cstruct`: a C problem struct to use instead of prob.c (same shapes; the fused path's centred points)."""

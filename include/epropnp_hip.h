@@ -28,7 +28,7 @@ extern "C" {
 #define EPROPNP_ELAUNCH (-2)  /* HIP launch/runtime error                                         */
 #define EPROPNP_ENODEV (-3)   /* no HIP device / not a gfx950 code object                         */
 
-#define EPROPNP_ABI_VERSION 6
+#define EPROPNP_ABI_VERSION 7
 
 /* Correspondences + camera + robust-cost parameters of one batch of objects.
  * Mirrors the state of PerspectiveCamera (epropnp/camera.py:35-62) and HuberPnPCost.delta
@@ -117,6 +117,26 @@ typedef struct epropnp_amis_params {
 /* Bytes of `split_scratch` with which epropnp_amis_forward would split the objects of this problem over workgroups
  * (0: it would not -- enough objects to fill the device, too few point tiles, or a shape the split does not serve). */
 uint64_t epropnp_amis_forward_split_bytes(const epropnp_problem* prob, int32_t mc_samples, int32_t num_iter);
+
+/* Launch plans: WHICH kernel instantiation a call would launch for a problem of these sizes.  Host functions that launch nothing and
+ * touch no device memory -- of `prob` only num_obj, num_pts, dof and whether lb / ub / delta_stats are non-NULL are read -- and
+ * that are the very functions the launchers decide with, so they cannot drift from what is launched.  The environment
+ * (EPROPNP_TUNE, EPROPNP_FWD_SPLIT, EPROPNP_*_PROJ) is read as a launch reads it.  num_cus: plan for a device of that many compute
+ * units (0: the current device).  They exist for tests and tuning tools: a test of an instantiation asserts through them that
+ * its shape still reaches that instantiation after the heuristics have changed.
+ *   epropnp_plan_amis_forward: has_scratch = the caller hands over epropnp_amis_forward_split_bytes() of split_scratch.
+ *     out[8] = {waves, point tiles resident per wave (0: the points stream through LDS), G workgroups per object, chunks the tiles
+ *               go through the registers in, bf16 projection, sampler state spilled to global scratch, pose tile truncated (a tile
+ *               holds less than one iteration's samples), the chunked instantiation is the one launched}
+ *   epropnp_plan_amis_backward: what epropnp_amis_backward (num_split 1) / epropnp_amis_backward_split launch.
+ *     out[5] = {waves, point tiles per wave and chunk, bf16 projection, grad_w2d rows parked in LDS for the delta fold,
+ *               the all-VALU kernel is taken instead (then the first four are 0)}
+ *   epropnp_plan_evaluate_cost: out[2] = {waves, points per lane} */
+int epropnp_plan_amis_forward(const epropnp_problem* prob, int32_t mc_samples, int32_t num_iter, int32_t has_scratch,
+                              int32_t num_cus, int32_t* out);
+int epropnp_plan_amis_backward(const epropnp_problem* prob, int32_t mc_samples, int32_t with_pose_init, int32_t num_split,
+                               int32_t num_cus, int32_t* out);
+int epropnp_plan_evaluate_cost(const epropnp_problem* prob, int32_t num_cus, int32_t* out);
 
 /* Everything EProPnPBase.monte_carlo_forward does between its arguments and its return tuple
  * (epropnp/epropnp.py:87-196): one host call that enqueues, in order,

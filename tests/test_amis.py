@@ -113,19 +113,26 @@ def test_logweights_consistent_with_own_samples(backend, dof, S, K, N):
 def test_forward_point_tiles_in_chunks_through_the_registers(backend, monkeypatch, N, bounds):
     """Beyond 48 point tiles per object the register-mode forward keeps 8 tiles per wave and takes the object's tiles through the
     registers in chunks of 32 per iteration (instead of 16 resident tiles per wave / 8-wave workgroups); EPROPNP_TUNE=fwd_no_chunks
-    keeps the old shapes.  Same samples in the first iteration (they do not depend on the sweep), costs to summation order."""
+    keeps the old shapes.  Same samples in the first iteration (they do not depend on the sweep), costs to summation order.
+    (EPROPNP_FWD_SPLIT=1: with so few objects a 256-CU device would deal the tiles to 4 or 8 workgroups, whose kernel knows no
+    chunks -- both runs were that same kernel once; the launch plan is asserted for that reason.)"""
     from epropnp import functional as F
     B, S, K, dof = 2, 64, 2, 6
+    monkeypatch.setenv('EPROPNP_FWD_SPLIT', '1')
     prob = orc.make_problem(B, N, dof, seed=51, bounds=bounds)
     noise = pack_noise(orc.make_noise(B, S, K, dof, seed=52), dof).to(backend)
     p, cam, cf = make_layer_objects(prob, backend)
     hp = F.PnPProblem(p['x3d'], p['x2d'], p['w2d'], cam, cf, dof)
     pose_opt, pose_cov, _ = F.lm_solve(hp, p['pose_init'], 3, with_pose_cov=True)
     set_tune(monkeypatch)
+    plan = F.launch_plan('forward', hp, S, K)
+    assert plan['chunks'] > 1 and plan['chunked'] and plan['G'] == 1 and (plan['waves'], plan['tiles']) == (4, 8), plan
     s1, w1 = F.amis_forward(hp, pose_opt, pose_cov, S, K, noise=noise)
     again = F.amis_forward(hp, pose_opt, pose_cov, S, K, noise=noise)
     assert torch.equal(s1, again[0]) and torch.equal(w1, again[1])
     set_tune(monkeypatch, fwd_no_chunks=True)
+    plan = F.launch_plan('forward', hp, S, K)
+    assert plan['chunks'] == 1 and not plan['chunked'] and plan['G'] == 1 and (plan['tiles'] == 16 or plan['waves'] == 8), plan
     s2, w2 = F.amis_forward(hp, pose_opt, pose_cov, S, K, noise=noise)
     s = S // K
     assert torch.equal(s1[:s], s2[:s])
@@ -136,9 +143,10 @@ def test_forward_point_tiles_in_chunks_through_the_registers(backend, monkeypatc
 
 @pytest.mark.parametrize('impl,N', [('valu', 150), ('mfma', 150), ('mfma', 300), ('mfma', 16), ('valu', 16), ('mfma', 17)])
 def test_backward_matches_autograd_of_oracle_at_fixed_samples(backend, monkeypatch, impl, N):
-    """The backward kernels alone (VALU sweep / MFMA projection; N=300 loops over two point chunks): arbitrary
-    upstream gradients, samples fixed -> compare with autograd through the oracle's evaluate (which is what the
-    reference's autograd replays)."""
+    """The backward kernels alone (VALU sweep / MFMA projection): arbitrary upstream gradients, samples fixed -> compare with
+    autograd through the oracle's evaluate (which is what the reference's autograd replays).  Each MFMA case launches twice: as
+    `backward_split` decides (N = 150: two workgroups per object; N = 300: four, 4 waves x 2 tiles each) and unsplit (nsplit = 1;
+    N = 300: 8 waves x 4 tiles, one chunk of 512 points)."""
     from epropnp import functional as F
     set_tune(monkeypatch, bwd_impl=impl)
     for dof, bounds in ((6, None), (4, 'tight'), (6, 'tight')):
@@ -167,10 +175,11 @@ def test_backward_matches_autograd_of_oracle_at_fixed_samples(backend, monkeypat
 
         p, cam, cf = make_layer_objects(prob, backend)
         hp = F.PnPProblem(p['x3d'], p['x2d'], p['w2d'], cam, cf, dof)
-        gx3d, gx2d, gw2d, gdel = F.amis_backward(hp, poses.to(backend), g_logw.to(backend), p['pose_init'],
-                                                 g_init.to(backend))
-        for mine, ref in ((gx3d, x3d.grad), (gx2d, x2d.grad), (gw2d, w2d.grad), (gdel, delta.grad)):
-            assert _rel(mine.cpu(), ref) <= 2e-4, (dof, bounds, _rel(mine.cpu(), ref))
+        for nsplit in ((None, 1) if impl == 'mfma' else (None,)):
+            gx3d, gx2d, gw2d, gdel = F.amis_backward(hp, poses.to(backend), g_logw.to(backend), p['pose_init'],
+                                                     g_init.to(backend), nsplit=nsplit)
+            for mine, ref in ((gx3d, x3d.grad), (gx2d, x2d.grad), (gw2d, w2d.grad), (gdel, delta.grad)):
+                assert _rel(mine.cpu(), ref) <= 2e-4, (dof, bounds, nsplit, _rel(mine.cpu(), ref))
 
 
 @pytest.mark.parametrize('delta,z_min', [(1e-4, 0.1), (3e3, 0.1), (0.7, 0.0), (0.7, 1e-6), (0.7, 4.5), (0.0, 0.1),

@@ -136,7 +136,9 @@ def test_lm_split_recomputes_missing_parts(backend, monkeypatch, dof, bounds, N,
     not there within EPROPNP_SPLIT_TIMEOUT_CYCLES is recomputed from its points by the same lanes in the same order.
     On the CPU emulation workgroups run one after another, so EVERY later part is missing for the earlier ones: the whole
     solve then goes through the recomputation path and must match the one-workgroup kernel to summation order.  On the GPU
-    a zero timeout forces the path wherever a sibling is not there at the first look: bit-identical to the patient run."""
+    a zero timeout forces the path wherever a sibling is not there at the first look: bit-identical to the patient run.
+    Against the one-workgroup kernel the GPU run is held to the strict form -- the same accept / reject history for every object,
+    pose and covariance compared for every object; only the emulation may let one object part ways at an equal cost."""
     from epropnp import functional as F
     B, L = 3, 4
     prob = orc.make_problem(B, N, dof, seed=77, bounds=bounds)
@@ -152,7 +154,7 @@ def test_lm_split_recomputes_missing_parts(backend, monkeypatch, dof, bounds, N,
     # the same accept / reject history -- except that a step of an already converged object changes the cost by rounding only
     # and is taken or not by the summation order: such an object may part ways, at an equal cost
     same = many[3] == one[3]
-    assert int(same.sum()) >= B - 1 and _close(many[2], one[2], 2e-5)
+    assert int(same.sum()) >= (B if backend.type == 'cuda' else B - 1) and _close(many[2], one[2], 2e-5)
     assert (many[0] - one[0])[same].abs().max().item() <= 2e-5
     assert _close(many[1][same], one[1][same], 2e-3)
     if backend.type == 'cuda':
