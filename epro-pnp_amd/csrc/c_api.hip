@@ -163,6 +163,22 @@ int epropnp_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_pa
                                          pose_opt, pose_samples, (hipStream_t)stream);
 }
 
+int epropnp_monte_carlo_forward_diag(const epropnp_problem* prob, const epropnp_mc_params* par, const float* pose_init,
+                                     const float* noise, float* x3d_centered, float* offset, float* pose_init_n,
+                                     float* start_pose, float* start_cost, float* pose_opt_n, float* pose_cov, float* cost,
+                                     float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
+                                     float* pose_samples, const epropnp_diag* diag, void* stream) {
+  return pnp::launch_monte_carlo_forward(prob, par, pose_init, noise, x3d_centered, offset, pose_init_n, start_pose,
+                                         start_cost, pose_opt_n, pose_cov, cost, pose_samples_n, logweights, cost_init,
+                                         pose_opt, pose_samples, (hipStream_t)stream, diag);
+}
+
+int epropnp_weight_stats(const float* logweights, int32_t mc_samples, int32_t num_obj, int32_t num_iter, float* stats,
+                         void* stream) {
+  pnp::StageScope prof_("weight_stats", (hipStream_t)stream);
+  return pnp::launch_weight_stats(logweights, mc_samples, num_obj, num_iter, stats, (hipStream_t)stream);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);
@@ -304,6 +320,16 @@ int epropnp_rslm_solve(const epropnp_problem* prob, const epropnp_lm_params* lm,
   pnp::StageScope prof_("rslm_solve", (hipStream_t)stream);
   return pnp::launch_rslm_solve(prob, lm, num_proposals, num_points, seed, offset, (const unsigned long long*)offset_dev,
                                 (const long long*)inds, rot, pose, cost, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int epropnp_rslm_solve_diag(const epropnp_problem* prob, const epropnp_lm_params* lm, int32_t num_proposals,
+                            int32_t num_points, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                            const int64_t* inds, const float* rot, float* pose, float* cost, void* scratch,
+                            uint64_t scratch_bytes, int32_t* winner, void* stream) {
+  pnp::StageScope prof_("rslm_solve", (hipStream_t)stream);
+  return pnp::launch_rslm_solve(prob, lm, num_proposals, num_points, seed, offset, (const unsigned long long*)offset_dev,
+                                (const long long*)inds, rot, pose, cost, scratch, scratch_bytes, (hipStream_t)stream, nullptr,
+                                nullptr, nullptr, nullptr, winner);
 }
 
 uint64_t epropnp_rslm_solve_scratch_bytes(const epropnp_problem* prob, int32_t num_proposals) {

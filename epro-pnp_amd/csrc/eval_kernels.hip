@@ -329,6 +329,103 @@ __global__ __launch_bounds__(512) void mc_loss_forward_kernel(const float* __res
   }
 }
 
+// Degeneracy of the importance weights per object (include/epropnp_hip.h: epropnp_weight_stats), in the decomposition of the loss
+// kernel above: a 512-thread block owns 16 adjacent columns, its 32 row groups (four per wave) each take every 32nd row of every
+// iteration's slice of S and meet in LDS.  Two passes over the column -- its maximum, then w = exp(logw - max) with ONE rounding in
+// the exponent's argument (an online rescaling would put two there, and the smallest iteration masses carry the argument's
+// rounding, 4e-6 at |logw| ~ 64, in full) -- the second of which finds the block's 32 KiB .. 256 KiB of log-weights in L2.  Every
+// sum runs in a fixed order (a thread's rows ascending, then the row groups ascending, then the iterations ascending) and nothing
+// is atomic: two launches agree to the last bit.
+// LDS: part[K][32][17] per-(iteration, row group) sums | sq[32][17] sums of squares, row maxima before | tot[K + 1][16].
+__global__ __launch_bounds__(512) void weight_stats_kernel(const float* __restrict__ logw, int S, int B, int K,
+                                                            float* __restrict__ stats) {
+  constexpr int CP = kLossCols + 1;
+  PNP_DYN_SMEM(float, lds);
+  float* part = lds;                              // [K][kLossRows][CP]
+  float* sq = part + (size_t)K * kLossRows * CP;  // [kLossRows][CP]
+  float* tot = sq + kLossRows * CP;               // [K + 1][kLossCols]: iteration masses, then the sum of squares
+  const int c = (int)(threadIdx.x % kLossCols), rg = (int)(threadIdx.x / kLossCols);
+  const int b = (int)blockIdx.x * kLossCols + c;
+  const int s_it = S / K;
+  const bool live = b < B;
+  // ---- pass 1: column maximum; NaN / +inf poison the column ----
+  float m = -INFINITY;
+  bool bad = false;
+  if (live) {
+    for (int j0 = rg; j0 < S; j0 += kLossRows * 8) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int j = j0 + k * kLossRows;
+        v[k] = (j < S) ? logw[(size_t)j * B + b] : -INFINITY;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        bad = bad || (v[k] != v[k]) || (v[k] == INFINITY);
+        m = (v[k] > m) ? v[k] : m;
+      }
+    }
+  }
+  sq[rg * CP + c] = bad ? NAN : m;
+  __syncthreads();
+  float M = -INFINITY;
+  for (int k = 0; k < kLossRows; ++k) {
+    const float mk = sq[k * CP + c];
+    bad = bad || (mk != mk);
+    M = fmaxf(M, mk);
+  }
+  __syncthreads();
+  // ---- pass 2: this row group's share of every iteration's sum of w, and of the sum of w^2 ----
+  const bool skip = !live || bad || M == -INFINITY;      // (-inf - -inf is a NaN: an empty column sums to zero by definition)
+  float acc2 = 0.f;
+  for (int it = 0; it < K; ++it) {
+    float acc = 0.f;
+    if (!skip) {
+      const int lo = it * s_it, hi = lo + s_it;
+      for (int j0 = lo + rg; j0 < hi; j0 += kLossRows * 4) {
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int j = j0 + k * kLossRows;
+          v[k] = (j < hi) ? logw[(size_t)j * B + b] : -INFINITY;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float w = (v[k] == M) ? 1.0f : expf(v[k] - M);      // (exp(-inf) = 0: padding and -inf samples)
+          acc += w;
+          acc2 = fmaf(w, w, acc2);
+        }
+      }
+    }
+    part[((size_t)it * kLossRows + rg) * CP + c] = acc;
+  }
+  sq[rg * CP + c] = acc2;
+  __syncthreads();
+  // ---- the 32 row groups of (iteration, column): thread (rg = iteration, c); row group 31 also takes the squares ----
+  for (int it = rg; it < K; it += kLossRows) {
+    float t = 0.f;
+    for (int k = 0; k < kLossRows; ++k) t += part[((size_t)it * kLossRows + k) * CP + c];
+    tot[it * kLossCols + c] = t;
+  }
+  if (rg == kLossRows - 1) {
+    float t = 0.f;
+    for (int k = 0; k < kLossRows; ++k) t += sq[k * CP + c];
+    tot[K * kLossCols + c] = t;
+  }
+  __syncthreads();
+  if (rg == 0 && live) {
+    float* row = stats + (size_t)b * (K + 3);
+    float sum = 0.f;
+    for (int it = 0; it < K; ++it) sum += tot[it * kLossCols + c];
+    const bool empty = M == -INFINITY;
+    const float inv = 1.0f / sum;
+    row[0] = bad ? NAN : (empty ? 0.f : sum * sum / tot[K * kLossCols + c]);
+    row[1] = bad ? NAN : (empty ? 0.f : inv);                   // the largest weight is exp(0)
+    row[2] = bad ? NAN : (empty ? -INFINITY : M + logf(sum));
+    for (int it = 0; it < K; ++it) row[3 + it] = bad ? NAN : (empty ? 0.f : tot[it * kLossCols + c] * inv);
+  }
+}
+
 // g == nullptr: the reduced loss (mc_loss_reduce_kernel) -- every object's upstream gradient is the scalar
 // grad_out[0] * coef[0] (* weight[b]), read from device memory so that the node stays capturable.
 __global__ __launch_bounds__(256) void mc_loss_backward_kernel(const float* __restrict__ logw, const float* __restrict__ lse,
@@ -970,6 +1067,19 @@ int launch_mc_loss_forward(const float* logw, const float* ct, int S, int B, flo
   if (!logw || !loss || !lse || S < 1) return fail(EPROPNP_EINVAL, "mc_loss_forward: bad argument");
   PNP_LAUNCH(mc_loss_forward_kernel, dim3((B + kLossCols - 1) / kLossCols), dim3(512), 0, st, logw, ct, S, B, loss, lse);
   return check_launch("mc_loss_forward_kernel");
+}
+
+constexpr int kWeightStatsMaxIter = 64;
+int launch_weight_stats(const float* logw, int S, int B, int K, float* stats, hipStream_t st) {
+  if (B <= 0) return EPROPNP_OK;
+  if (!logw || !stats) return fail(EPROPNP_EINVAL, "weight_stats: NULL pointer");
+  if (K < 1 || K > kWeightStatsMaxIter || S < K || S % K != 0)
+    return fail(EPROPNP_EINVAL, "weight_stats: mc_samples (%d) must be a positive multiple of num_iter (%d) in [1, %d]", S, K,
+                kWeightStatsMaxIter);
+  const size_t smem = sizeof(float) * ((size_t)(K + 1) * kLossRows * (kLossCols + 1) + (size_t)(K + 1) * kLossCols);
+  allow_dynamic_lds(reinterpret_cast<const void*>(weight_stats_kernel), smem);
+  PNP_LAUNCH(weight_stats_kernel, dim3((B + kLossCols - 1) / kLossCols), dim3(512), smem, st, logw, S, B, K, stats);
+  return check_launch("weight_stats_kernel");
 }
 
 int launch_mc_loss_backward(const float* logw, const float* lse, const float* loss, const float* g, int S, int B,

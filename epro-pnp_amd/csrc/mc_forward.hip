@@ -33,11 +33,25 @@ __global__ __launch_bounds__(256) void select_start_kernel(const float* __restri
   if (cost_init[b] < start_cost[b]) start_pose[i] = pose_init[i];
 }
 
+// (diagnostics) where the cheaper-of-two selection kept pose_init, no proposal was handed on: winner = -1.  The comparison is the
+// selection's own, on the same two cost arrays (start_cost keeps the RSLM cost either way).
+__global__ __launch_bounds__(256) void mark_kept_init_kernel(const float* __restrict__ cost_init,
+                                                             const float* __restrict__ start_cost, int* __restrict__ winner,
+                                                             int B) {
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b < B && cost_init[b] < start_cost[b]) winner[b] = -1;
+}
+
 int launch_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_params* par, const float* pose_init,
                                const float* noise, float* x3d_centered, float* offset, float* pose_init_n,
                                float* start_pose, float* start_cost, float* pose_opt_n, float* pose_cov, float* cost,
                                float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
-                               float* pose_samples, hipStream_t st) {
+                               float* pose_samples, hipStream_t st, const epropnp_diag* diag) {
+  // diagnostics (include/epropnp_hip.h: epropnp_diag); all NULL = the plain call, launch for launch
+  int32_t* const d_accept = diag ? diag->lm_accept_mask : nullptr;
+  int32_t* const d_winner = (diag && par && par->init_mode != 0) ? diag->rslm_winner : nullptr;
+  float* const d_props = diag ? diag->proposals : nullptr;
+  float* const d_wstats = diag ? diag->weight_stats : nullptr;
   if (int rc = check_problem(prob)) return rc;
   if (!par) return fail(EPROPNP_EINVAL, "monte_carlo_forward: params NULL");
   if (prob->num_obj == 0) return EPROPNP_OK;
@@ -98,7 +112,9 @@ int launch_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_par
                                 (const unsigned long long*)par->rslm_offset_dev, (const long long*)par->rslm_inds,
                                 par->rslm_rot, start_pose, start_cost, par->rslm_scratch, par->rslm_scratch_bytes, st,
                                 par->init_mode == 2 ? pinit : nullptr, par->init_mode == 2 ? cost_init : nullptr, &selected,
-                                &sel.parts)))
+                                // a winner index is reported by the initialiser's own reduce launch: the selection is not deferred
+                                // to the LM launch then (the same argmin, ties to the lowest part, and the same rival rule: same pose)
+                                d_winner ? nullptr : &sel.parts, d_winner)))
       return rc;
     if (sel.parts >= 1) {     // no reduce / select launch was made: the LM kernel picks the winner itself
       sel.cand = (const float*)par->rslm_scratch;
@@ -109,18 +125,26 @@ int launch_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_par
                  B, PL);
       if ((rc = check_launch("select_start_kernel"))) return rc;
     }
+    if (par->init_mode == 2 && d_winner) {
+      PNP_LAUNCH(mark_kept_init_kernel, dim3((B + 255) / 256), dim3(256), 0, st, cost_init, (const float*)start_cost, (int*)d_winner, B);
+      if ((rc = check_launch("mark_kept_init_kernel"))) return rc;
+    }
     start = start_pose;
   }
-  { StageScope ps("lm_solve", st); if ((rc = launch_lm_solve(&q, &par->lm, start, pose_opt_n, pose_cov, cost, nullptr, par->lm_scratch, par->lm_scratch_bytes, st, sel.cand ? &sel : nullptr))) return rc; }
-  {   // normalize: pnp_denormalize (common.py:127-136) of pose_opt and of the samples rides in the AMIS launch
+  { StageScope ps("lm_solve", st); if ((rc = launch_lm_solve(&q, &par->lm, start, pose_opt_n, pose_cov, cost, d_accept, par->lm_scratch, par->lm_scratch_bytes, st, sel.cand ? &sel : nullptr))) return rc; }
+  // normalize: pnp_denormalize (common.py:127-136) of pose_opt and of the samples rides in the AMIS launch
+  const bool fold = par->normalize && !tune_flag("no_denorm_fold");
+  {
     const DenormOut dn = {offset, pose_samples, pose_opt};
-    const bool fold = par->normalize && !tune_flag("no_denorm_fold");
     StageScope ps("amis_forward", st);
-    if ((rc = launch_amis_forward(&q, &par->amis, pose_opt_n, pose_cov, noise, pose_samples_n, logweights, nullptr, st, fold ? &dn : nullptr)))
+    if ((rc = launch_amis_forward(&q, &par->amis, pose_opt_n, pose_cov, noise, pose_samples_n, logweights, d_props, st, fold ? &dn : nullptr)))
       return rc;
-    if (fold) return EPROPNP_OK;
   }
-  if (par->normalize) {       // (EPROPNP_TUNE=no_denorm_fold: the separate launch, same bits)
+  if (d_wstats) {
+    StageScope ps("weight_stats", st);
+    if ((rc = launch_weight_stats(logweights, S, B, par->amis.num_iter, d_wstats, st))) return rc;
+  }
+  if (par->normalize && !fold) {       // (EPROPNP_TUNE=no_denorm_fold: the separate launch, same bits)
     StageScope ps("shift_poses", st);
     if ((rc = launch_shift_poses_pair(pose_opt_n, pose_opt, 1, pose_samples_n, pose_samples, S, offset, B, prob->dof, -1.0f, st)))
       return rc;

@@ -216,7 +216,7 @@ int launch_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_par
                                const float* noise, float* x3d_centered, float* offset, float* pose_init_n,
                                float* start_pose, float* start_cost, float* pose_opt_n, float* pose_cov, float* cost,
                                float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
-                               float* pose_samples, hipStream_t st);
+                               float* pose_samples, hipStream_t st, const epropnp_diag* diag = nullptr);
 unsigned long long amis_forward_split_bytes(const epropnp_problem* prob, int mc_samples, int num_iter);
 // launch plans as int records (include/epropnp_hip.h: epropnp_plan_*): host only, nothing is launched
 int plan_amis_forward_record(const epropnp_problem* prob, int S, int K, unsigned long long scratch_bytes, int32_t* out);
@@ -233,7 +233,7 @@ int launch_rslm_solve(const epropnp_problem* prob, const epropnp_lm_params* lm, 
                       unsigned long long offset, const unsigned long long* offset_dev, const long long* inds, const float* rot,
                       float* pose_out, float* cost_out, void* scratch, unsigned long long scratch_bytes,
                       hipStream_t st, const float* rival_pose = nullptr, const float* rival_cost = nullptr,
-                      bool* rival_taken = nullptr, int* deferred_parts = nullptr);
+                      bool* rival_taken = nullptr, int* deferred_parts = nullptr, int32_t* winner = nullptr);
 unsigned long long rslm_scratch_bytes(const epropnp_problem* prob, int num_proposals);
 int launch_shift_poses_pair(const float* pose_a, float* out_a, int Pa, const float* pose_b, float* out_b, int Pb,
                             const float* offset, int B, int dof, float sign, hipStream_t st);
@@ -267,6 +267,7 @@ int launch_rslm_draw(const float* w2d, int B, int N, int P, int n_pts, unsigned 
 int launch_adaptive_delta(const float* x2d, const float* w2d, int B, int N, float rel, float* delta, float* stats,
                           hipStream_t st);
 int launch_mc_loss_forward(const float* logw, const float* ct, int S, int B, float* loss, float* lse, hipStream_t st);
+int launch_weight_stats(const float* logw, int S, int B, int K, float* stats, hipStream_t st);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

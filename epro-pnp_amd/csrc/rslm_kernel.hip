@@ -33,13 +33,17 @@ Problem p, LmParams lm, int P, int n_pts, unsigned long long seed,
                                                           const unsigned long long* __restrict__ offset_dev,
                                                           const long long* __restrict__ inds,
                                                           const float* __restrict__ rot, float* __restrict__ pose_out,
-                                                          float* __restrict__ cost_out, int parts, float* __restrict__ cand_out, int to_cand) {
+                                                          float* __restrict__ cost_out, int parts, float* __restrict__ cand_out, int to_cand,
+                                                          int* __restrict__ winner_out) {
   constexpr int PL = PoseLen<DOF>::value;
   constexpr int NV = NormalEq<DOF>::NV;
   // parts > 1: the proposals of an object are dealt to `parts` workgroups (v = b * parts + part), each keeps the best of its
   // share and writes it to cand_out[part][b][PL + 1]; rslm_reduce_kernel picks the winner.  An object's 64 proposals are
   // four rounds of one workgroup: at 600 objects on 256 CUs a CU gets two or three such workgroups (as long as 768 objects
   // take), and at <= 256 objects the rounds in sequence are the whole run time (profiles/r03_rslm_parts.txt).
+  // winner_out (diagnostics, or nullptr): the index in [0, P) of the proposal whose pose is handed on -- carried next to best_cost
+  // through the rounds and the 16-row argmin.  parts > 1: a part's index waits in pose_out[b][part] (its bits; parts <= 4 <=
+  // pose_len, and rslm_reduce_kernel reads an object's slots before it writes the object's pose over them).
   const int v = object_of_block(p.B * parts);
   if (v >= p.B * parts) return;
   const int b = v / parts, part = v - b * parts;
@@ -119,6 +123,7 @@ Problem p, LmParams lm, int P, int n_pts, unsigned long long seed,
   const float delta_v = to_vgpr(delta), zmin_v = to_vgpr(p.z_min), inv_eps_v = to_vgpr(p.inv_huber_eps);
 
   float best_cost = INFINITY, best_pose[PL];
+  int best_idx = P_lo;
 #pragma unroll
   for (int i = 0; i < PL; ++i) best_pose[i] = 0.f;
   float* mykey = key + row * Np;
@@ -251,6 +256,7 @@ Problem p, LmParams lm, int P, int n_pts, unsigned long long seed,
     PNP_PHASE(4);
     if (active && (j0 == P_lo || c < best_cost)) {
       best_cost = c;
+      best_idx = j;
 #pragma unroll
       for (int i = 0; i < PL; ++i) best_pose[i] = pose[i];
     }
@@ -259,7 +265,9 @@ Problem p, LmParams lm, int P, int n_pts, unsigned long long seed,
   // ---- argmin over the 16 rows (ties: lowest row = lowest proposal index of the first round) ----
   __syncthreads();
   float* cand = red;      // [16][PL + 1]
+  int* cand_idx = reinterpret_cast<int*>(key);      // [16] (the key rows are done with)
   if (l16 == 0) {
+    cand_idx[row] = best_idx;
     cand[row * (PL + 1)] = (row < P_hi - P_lo) ? best_cost : INFINITY;
 #pragma unroll
     for (int i = 0; i < PL; ++i) cand[row * (PL + 1) + 1 + i] = best_pose[i];
@@ -277,10 +285,12 @@ Problem p, LmParams lm, int P, int n_pts, unsigned long long seed,
       dst[0] = wc;
 #pragma unroll
       for (int i = 0; i < PL; ++i) dst[1 + i] = cand[w * (PL + 1) + 1 + i];
+      if (winner_out) pose_out[(size_t)b * PL + part] = bits_f32((unsigned)cand_idx[w]);
     } else {
 #pragma unroll
       for (int i = 0; i < PL; ++i) pose_out[(size_t)b * PL + i] = cand[w * (PL + 1) + 1 + i];
       if (cost_out) cost_out[b] = wc;
+      if (winner_out) winner_out[b] = cand_idx[w];
     }
   }
   PNP_PHASES_FLUSH(6);
@@ -294,9 +304,10 @@ template <int PL>
 __global__ __launch_bounds__(256) void rslm_reduce_kernel(const float* __restrict__ cand, int B, int parts,
                                                           float* __restrict__ pose_out, float* __restrict__ cost_out,
                                                           const float* __restrict__ rival_pose,
-                                                          const float* __restrict__ rival_cost) {
+                                                          const float* __restrict__ rival_cost, int* __restrict__ winner_out) {
   const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (b >= B) return;
+  static_assert(PL >= 4, "the parts' proposal indices wait in the object's pose slots");
   int w = 0;
   float wc = cand[(size_t)b * (PL + 1)];
   for (int q = 1; q < parts; ++q) {
@@ -304,6 +315,8 @@ __global__ __launch_bounds__(256) void rslm_reduce_kernel(const float* __restric
     if (c < wc) { wc = c; w = q; }
   }
   const float* src = cand + ((size_t)w * B + b) * (PL + 1) + 1;
+  // (diagnostics) the winning part's own winner, parked in pose_out[b][part] by rslm_solve_kernel: read before the pose goes there
+  if (winner_out != nullptr) winner_out[b] = (int)f32_bits(pose_out[(size_t)b * PL + (w & 3)]);
   if (rival_pose != nullptr && rival_cost[b] < wc) src = rival_pose + (size_t)b * PL;     // (cost_out keeps the RSLM cost)
 #pragma unroll
   for (int i = 0; i < PL; ++i) pose_out[(size_t)b * PL + i] = src[i];
@@ -335,7 +348,9 @@ unsigned long long rslm_scratch_bytes(const epropnp_problem* prob, int P) {
 int launch_rslm_solve(const epropnp_problem* prob, const epropnp_lm_params* lm, int P, int n_pts, unsigned long long seed,
                       unsigned long long offset, const unsigned long long* offset_dev, const long long* inds, const float* rot,
                       float* pose_out, float* cost_out, void* scratch, unsigned long long scratch_bytes, hipStream_t st,
-                      const float* rival_pose, const float* rival_cost, bool* rival_taken, int* deferred_parts) {
+                      const float* rival_pose, const float* rival_cost, bool* rival_taken, int* deferred_parts, int32_t* winner) {
+  // winner != nullptr (diagnostics): winner[b] = index in [0, P) of the proposal whose pose lands in pose_out, by the tie rules of
+  // the argmins as they are; never combined with deferred_parts (the LM launch's own selection reports no index).
   // deferred_parts != nullptr (and a scratch that holds the candidates): the reduce launch is LEFT OUT and *deferred_parts = parts
   // (>= 1) tells the caller to hand `scratch` to the LM launch as its start selection (lm_core.h: StartSelect); pose_out / cost_out
   // are then not written.  *deferred_parts = 0: pose_out holds the start as usual.
@@ -361,11 +376,12 @@ int launch_rslm_solve(const epropnp_problem* prob, const epropnp_lm_params* lm, 
   int parts = rslm_parts(d.B, P);
   const int PLh = prob->dof == 6 ? 7 : 4;
   if (parts > 1 && (scratch == nullptr || scratch_bytes < sizeof(float) * (size_t)parts * d.B * (PLh + 1))) parts = 1;
+  if (winner != nullptr && deferred_parts != nullptr) return fail(EPROPNP_EINVAL, "rslm_solve: winner with a deferred selection");
   const bool to_cand = deferred_parts != nullptr && scratch != nullptr && scratch_bytes >= sizeof(float) * (size_t)parts * d.B * (PLh + 1);
   const dim3 grid(padded_object_grid(d.B * parts)), block(256);
   dispatch_dof_bounds(prob->dof, has_bounds(prob), [&](auto DOF, auto BND) -> int {
     PNP_LAUNCH((rslm_solve_kernel<decltype(DOF)::value, decltype(BND)::value>), grid, block, smem, st, d, k, P, n_pts, seed,
-               offset, offset_dev, inds, rot, pose_out, cost_out, parts, (float*)scratch, (int)to_cand);
+               offset, offset_dev, inds, rot, pose_out, cost_out, parts, (float*)scratch, (int)to_cand, (int*)winner);
     return 0;
   });
   if (to_cand) {
@@ -378,10 +394,10 @@ int launch_rslm_solve(const epropnp_problem* prob, const epropnp_lm_params* lm, 
     const dim3 rgrid((d.B + 255) / 256);
     if (prob->dof == 6) {
       PNP_LAUNCH((rslm_reduce_kernel<7>), rgrid, block, 0, st, (const float*)scratch, d.B, parts, pose_out, cost_out, rival_pose,
-                 rival_cost);
+                 rival_cost, (int*)winner);
     } else {
       PNP_LAUNCH((rslm_reduce_kernel<4>), rgrid, block, 0, st, (const float*)scratch, d.B, parts, pose_out, cost_out, rival_pose,
-                 rival_cost);
+                 rival_cost, (int*)winner);
     }
     if (rival_taken) *rival_taken = rival_pose != nullptr && rival_cost != nullptr;
   }

@@ -64,6 +64,12 @@ class McParams(C.Structure):
                 ('rslm_scratch_bytes', C.c_uint64), ('lm_scratch', C.c_void_p), ('lm_scratch_bytes', C.c_uint64)]
 
 
+class Diag(C.Structure):
+    """epropnp_diag: optional per-object diagnostics of epropnp_monte_carlo_forward_diag (device pointers, None = not wanted)"""
+    _fields_ = [('lm_accept_mask', C.c_void_p), ('rslm_winner', C.c_void_p), ('proposals', C.c_void_p),
+                ('weight_stats', C.c_void_p)]
+
+
 ABI_VERSION = 7
 _lib = None
 
@@ -84,6 +90,8 @@ def _declare(lib):
     lib.epropnp_async_status_word.restype = C.POINTER(C.c_int32)
     lib.epropnp_profile_read.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     lib.epropnp_monte_carlo_forward.argtypes = [C.POINTER(Problem), C.POINTER(McParams)] + [vp] * 16
+    lib.epropnp_monte_carlo_forward_diag.argtypes = [C.POINTER(Problem), C.POINTER(McParams)] + [vp] * 15 + [C.POINTER(Diag), vp]
+    lib.epropnp_weight_stats.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.epropnp_evaluate_cost.argtypes = [C.POINTER(Problem), vp, i32, vp, vp]
     lib.epropnp_normal_equations.argtypes = [C.POINTER(Problem), vp, i32, vp, vp, vp, vp]
     lib.epropnp_cost_pose_cam_grad.argtypes = [C.POINTER(Problem), vp, vp, i32, i32, vp, vp, vp]
@@ -107,6 +115,8 @@ def _declare(lib):
     lib.epropnp_prepare_dense_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.epropnp_rslm_solve.argtypes = [C.POINTER(Problem), C.POINTER(LmParams), i32, i32, C.c_uint64, C.c_uint64, vp, vp, vp,
                                        vp, vp, vp, C.c_uint64, vp]
+    lib.epropnp_rslm_solve_diag.argtypes = [C.POINTER(Problem), C.POINTER(LmParams), i32, i32, C.c_uint64, C.c_uint64, vp, vp, vp,
+                                            vp, vp, vp, C.c_uint64, vp, vp]
     lib.epropnp_rslm_solve_scratch_bytes.argtypes = [C.POINTER(Problem), i32]
     lib.epropnp_rslm_solve_scratch_bytes.restype = C.c_uint64
     lib.epropnp_adaptive_delta.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp]
@@ -118,7 +128,8 @@ def _declare(lib):
     for name in ('evaluate_cost', 'normal_equations', 'lm_solve', 'amis_forward', 'amis_backward', 'adaptive_delta',
                  'mc_loss_forward', 'mc_loss_backward', 'rslm_draw', 'gn_step_forward', 'gn_step_backward', 'rslm_solve', 'center_points', 'shift_poses', 'prepare_forward', 'prepare_backward', 'pose_opt_plus_forward', 'pose_opt_plus_backward', 'shift_poses_backward', 'prepare_dense_forward',
                  'prepare_dense_backward', 'amis_backward_split', 'monte_carlo_forward', 'cost_pose_cam_grad', 'mc_loss_reduce',
-                 'mc_loss_reduce_backward', 'plan_amis_forward', 'plan_amis_backward', 'plan_evaluate_cost'):
+                 'mc_loss_reduce_backward', 'plan_amis_forward', 'plan_amis_backward', 'plan_evaluate_cost',
+                 'monte_carlo_forward_diag', 'weight_stats', 'rslm_solve_diag'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -134,7 +145,8 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_monte_carlo_forward', 'epropnp_cost_pose_cam_grad', 'epropnp_async_status',
            'epropnp_async_status_word', 'epropnp_amis_forward_split_bytes', 'epropnp_rslm_solve_scratch_bytes',
            'epropnp_lm_solve_split_bytes', 'epropnp_mc_loss_reduce', 'epropnp_mc_loss_reduce_backward', 'epropnp_exchange_pack',
-           'epropnp_plan_amis_forward', 'epropnp_plan_amis_backward', 'epropnp_plan_evaluate_cost')
+           'epropnp_plan_amis_forward', 'epropnp_plan_amis_backward', 'epropnp_plan_evaluate_cost',
+           'epropnp_monte_carlo_forward_diag', 'epropnp_weight_stats', 'epropnp_rslm_solve_diag')
 
 
 def lib():

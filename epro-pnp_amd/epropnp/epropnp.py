@@ -31,6 +31,17 @@ def _DetachedCamera(camera):
     return cam
 
 
+class _NoBlock:
+    """`with` placeholder outside a diagnostics() block"""
+    records = ()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
 def cholesky_wrapper(mat, default_diag=None, force_cpu=True):
     """Batched Cholesky; matrices that are not positive definite yield diag(default_diag) (or I).
     Kept for API compatibility (reference: epropnp/epropnp.py:16-33); the AMIS kernel has its own in-register
@@ -190,16 +201,24 @@ class EProPnPBase(torch.nn.Module):
         if pose_init is not None and num_obj > 0:
             cost_init_value = hip.evaluate_cost(prob, pose_init)
 
-        with hip.share_problem(prob, x3d, x2d, w2d, camera, cost_fun):
+        sink = hip.diagnostics.sink() if num_obj > 0 else None
+        with hip.share_problem(prob, x3d, x2d, w2d, camera, cost_fun), (hip.diagnostics() if sink is not None else _NoBlock()) as inner:
             pose_opt, pose_cov, cost, pose_opt_plus = self.solver(
                 x3d, x2d, w2d, camera, cost_fun, pose_init=pose_init, cost_init=cost_init_value, with_pose_cov=True,
                 force_init_solve=force_init_solve, normalize_override=False, **kwargs)
 
         if num_obj > 0:
             delta = cost_fun.delta
+            cfg = self._amis_config(noise)
             out = hip.monte_carlo_cost(x3d, x2d, w2d, delta if isinstance(delta, torch.Tensor) else None, prob,
-                                       pose_opt, pose_cov, pose_init, cost_init_value, self._amis_config(noise))
+                                       pose_opt, pose_cov, pose_init, cost_init_value, cfg)
             pose_samples, pose_sample_logweights = out[0], out[1]
+            if sink is not None:        # this call's ONE record: the solver's two fields + the sampler's
+                rec = inner.records[-1] if inner.records else hip.DiagRecord()
+                with torch.no_grad():   # (the composite path's sampler node has no proposal output: the same draws once more)
+                    rec.proposals = hip.amis_forward(prob, pose_opt, pose_cov, with_proposals=True, **cfg)[2]
+                    rec.weight_stats = hip.weight_stats(pose_sample_logweights.detach(), self.num_iter)
+                sink.records.append(rec)
             cost_init = out[2] if pose_init is not None else None
             if self.rng_counter is not None and noise is None:
                 self.rng_counter.add_(1)          # in-stream: part of a captured graph
@@ -302,7 +321,7 @@ class EProPnPBase(torch.nn.Module):
             par.amis.advance_count = 2 if (bump_self and bump_init) else 1
         try:
             pose_opt, samples, logw, cost, cost_init, pose_opt_n, x3d_c, offset = hip.fused_monte_carlo(
-                x3d, x2d, w2d, None if fold else delta, prob, pose_init, par, noise, bool(with_cost))
+                x3d, x2d, w2d, None if fold else delta, prob, pose_init, par, noise, bool(with_cost), hip.diagnostics.sink())
         except Exception:
             # A call that failed between its launches may have left the advance ticket part-way (some workgroups counted, the last
             # one never arrived): every later step would then miss or mis-time the counters' increment and REUSE its samples in

@@ -99,6 +99,99 @@ class numerics_check:
         return False
 
 
+# ---- per-object solver / sampler diagnostics ---------------------------------------------------------------------
+_diag = threading.local()
+
+
+def chol_fallback(proposals):
+    """(B,K,40) fitted proposal records -> (B,K,2) bool: [translation covariance, ACG shape matrix] of iteration k's proposal was
+    not positive definite and cholesky_wrapper's default took its place (epropnp.py:16-33; slots 37 / 38 of the record)."""
+    return proposals[..., 37:39] != 0
+
+
+class DiagRecord:
+    """What one call inside a `diagnostics()` block decided, per object; device tensors, nothing synchronised.
+
+    lm_accept_mask (B,) int32 | None   bit i = LM step i of the main solve was accepted (the reference's `step_is_successful`,
+                                       levenberg_marquardt.py:227-229); None in fast_mode (Gauss-Newton accepts every step)
+    rslm_winner    (B,) int32 | None   index of the random-sample proposal the main solve started from (the reference's
+                                       `min_cost_ind`, :346-347), -1 where pose_init was cheaper (:124-130); None without an init solve
+    proposals      (B,K,40) | None     the K fitted AMIS proposals (amis_forward's `proposals`); chol_fallback (B,K,2) from it
+    weight_stats   (B,K+3)  | None     F.weight_stats of the call's log-weights: ess, max_weight_share, log_evidence, iter_mass
+    Solver-only calls (LMSolver.solve, EProPnP*.forward) fill the first two."""
+    __slots__ = ('lm_accept_mask', 'rslm_winner', 'proposals', 'weight_stats')
+
+    def __init__(self, lm_accept_mask=None, rslm_winner=None, proposals=None, weight_stats=None):
+        self.lm_accept_mask, self.rslm_winner, self.proposals, self.weight_stats = lm_accept_mask, rslm_winner, proposals, weight_stats
+
+    @property
+    def chol_fallback(self):
+        return None if self.proposals is None else chol_fallback(self.proposals)
+
+    def _stat(self, sl):
+        return None if self.weight_stats is None else self.weight_stats[:, sl]
+
+    ess = property(lambda self: self._stat(0))                    # (sum w)^2 / sum w^2, in [1, S]
+    max_weight_share = property(lambda self: self._stat(1))       # max w / sum w
+    log_evidence = property(lambda self: self._stat(2))           # logsumexp of the log-weights (the MC loss adds cost_target to it)
+    iter_mass = property(lambda self: self._stat(slice(3, None)))     # (B,K) share of each AMIS iteration's samples in sum w
+
+
+class diagnostics:
+    """Context manager: every `monte_carlo_forward` / `LMSolver.solve` call made inside appends one DiagRecord to `.records`:
+
+        with epropnp.functional.diagnostics() as diag:
+            out = layer.monte_carlo_forward(x3d, x2d, w2d, camera, cost_fun, pose_init=...)
+        rec = diag.records[-1]
+
+    The outputs and gradients of the calls are bit-identical to those outside the block; the fused forward goes through
+    epropnp_monte_carlo_forward_diag (one more small launch for the weight statistics).  Outside a block nothing changes.  Not
+    supported inside a hipGraph capture: calls made while the stream captures, and GraphedLoss, record nothing."""
+
+    def __init__(self):
+        self.records = []
+
+    @staticmethod
+    def sink():
+        """The innermost active block of this thread, or None (also None while the current stream is being captured)."""
+        d = getattr(_diag, 'sink', None)
+        if d is not None and _hip._gpu_present() and torch.cuda.is_current_stream_capturing():
+            return None
+        return d
+
+    def __enter__(self):
+        self.prev = getattr(_diag, 'sink', None)
+        _diag.sink = self
+        return self
+
+    def __exit__(self, *exc):
+        _diag.sink = self.prev
+        return False
+
+    class paused:
+        """No recording inside (sub-problem solves of the composite initialiser, GraphedLoss's warm-up and capture)."""
+
+        def __enter__(self):
+            self.prev = getattr(_diag, 'sink', None)
+            _diag.sink = None
+            return self
+
+        def __exit__(self, *exc):
+            _diag.sink = self.prev
+            return False
+
+
+def weight_stats(logweights, num_iter):
+    """Degeneracy of importance weights per object.  logweights (S,B) = num_iter AMIS iterations of S / num_iter consecutive
+    samples -> stats (B, 3 + num_iter) = [ess, max_share, lse, mass_0 .. mass_{K-1}] (include/epropnp_hip.h: epropnp_weight_stats)."""
+    lw = _f32c(logweights, 'logweights')
+    S, B = lw.shape
+    K = int(num_iter)
+    stats = torch.empty((B, K + 3), dtype=torch.float32, device=lw.device)
+    _hip.call('epropnp_weight_stats', _hip.ptr(lw), S, B, K, _hip.ptr(stats), _hip.stream_of(lw))
+    return stats
+
+
 class PnPProblem:
     """Contiguous fp32 device views of one batch of correspondences + camera + Huber threshold.
 
@@ -549,7 +642,7 @@ class _FusedMonteCarlo(torch.autograd.Function):
     Backward: the same recompute kernel as _MonteCarloCost, in the solver's (normalised) frame."""
 
     @staticmethod
-    def forward(ctx, x3d, x2d, w2d, delta, prob, pose_init, par, noise, with_cost):
+    def forward(ctx, x3d, x2d, w2d, delta, prob, pose_init, par, noise, with_cost, diag=None):
         B, N, PL, d = prob.B, prob.N, prob.pose_len, prob.dof
         S = par.amis.mc_samples
         new = prob.new
@@ -568,9 +661,19 @@ class _FusedMonteCarlo(torch.autograd.Function):
         cost_init = new(B) if pin is not None else None
         pose_opt, samples = (new(B, PL), new(S, B, PL)) if normalize else (None, None)     # caller's frame
         p = _hip.ptr
-        _hip.call('epropnp_monte_carlo_forward', C.byref(prob.c), C.byref(par), p(pin), p(nz), p(x3d_c), p(offset), p(pin_n),
-                  p(start_pose), p(start_cost), p(pose_opt_n), p(pose_cov), p(cost), p(samples_n), p(logw), p(cost_init),
-                  p(pose_opt), p(samples), prob.stream)
+        if diag is None:
+            _hip.call('epropnp_monte_carlo_forward', C.byref(prob.c), C.byref(par), p(pin), p(nz), p(x3d_c), p(offset), p(pin_n),
+                      p(start_pose), p(start_cost), p(pose_opt_n), p(pose_cov), p(cost), p(samples_n), p(logw), p(cost_init),
+                      p(pose_opt), p(samples), prob.stream)
+        else:       # inside a `diagnostics()` block: the same launches plus the record's tensors
+            K = par.amis.num_iter
+            rec = DiagRecord(None if par.lm.fast_mode else new(B, dtype=torch.int32),
+                             new(B, dtype=torch.int32) if par.init_mode else None, new(B, K, 40), new(B, K + 3))
+            dg = _hip.Diag(p(rec.lm_accept_mask), p(rec.rslm_winner), p(rec.proposals), p(rec.weight_stats))
+            _hip.call('epropnp_monte_carlo_forward_diag', C.byref(prob.c), C.byref(par), p(pin), p(nz), p(x3d_c), p(offset),
+                      p(pin_n), p(start_pose), p(start_cost), p(pose_opt_n), p(pose_cov), p(cost), p(samples_n), p(logw),
+                      p(cost_init), p(pose_opt), p(samples), C.byref(dg), prob.stream)
+            diag.records.append(rec)
         if normalize:      # the backward differentiates the cost in the solver frame: same problem, centred points
             bprob = _hip.Problem.from_buffer_copy(prob.c)       # (prob.fold_delta travels with the copy)
             bprob.x3d = x3d_c.data_ptr()
@@ -589,7 +692,7 @@ class _FusedMonteCarlo(torch.autograd.Function):
         (samples_n,) = ctx.saved_tensors
         prob = ctx.prob
         if g_logw is None and g_cost_init is None:
-            return (None,) * 9
+            return (None,) * 10
         _check_inputs(ctx)
         if g_logw is None:
             g_logw = torch.full(samples_n.shape[:2], 0.0, dtype=torch.float32, device=samples_n.device)
@@ -600,13 +703,14 @@ class _FusedMonteCarlo(torch.autograd.Function):
         if ctx.delta_shape is not None and ctx.needs_input_grad[3]:
             gdelta = gdel.sum() if len(ctx.delta_shape) == 0 else gdel.reshape(ctx.delta_shape)
         return (gx3d if ctx.needs_input_grad[0] else None, gx2d if ctx.needs_input_grad[1] else None,
-                gw2d if ctx.needs_input_grad[2] else None, gdelta, None, None, None, None, None)
+                gw2d if ctx.needs_input_grad[2] else None, gdelta, None, None, None, None, None, None)
 
 
-def fused_monte_carlo(x3d, x2d, w2d, delta, prob, pose_init, par, noise, with_cost):
+def fused_monte_carlo(x3d, x2d, w2d, delta, prob, pose_init, par, noise, with_cost, diag=None):
     """-> pose_opt, pose_samples, logweights, cost | None, cost_init | None, and the solver frame: pose_opt_n,
-    (x3d_centered, offset) | (None, None)"""
-    ext = _hip.torch_ext()
+    (x3d_centered, offset) | (None, None).  diag: the active `diagnostics()` block, which receives the call's DiagRecord (the ctypes
+    node then: the C++ node has no diagnostics entry; same kernels, same bits)."""
+    ext = _hip.torch_ext() if diag is None else None
     if ext is not None:      # C++ autograd node over the same entry point (csrc/torch_binding.cpp)
         if noise is not None:
             assert noise.shape == (prob.B, par.amis.num_iter, par.amis.mc_samples // par.amis.num_iter, noise_stride(prob.dof)), \
@@ -622,7 +726,7 @@ def fused_monte_carlo(x3d, x2d, w2d, delta, prob, pose_init, par, noise, with_co
     else:
         assert prob.delta_fold is None or delta is None, 'a folded delta takes no gradient from this node'
         pose_opt_n, samples_n, logw, cost, cost_init, pose_opt, samples, x3d_c, offset = _FusedMonteCarlo.apply(
-            x3d, x2d, w2d, delta, prob, pose_init, par, noise, with_cost)
+            x3d, x2d, w2d, delta, prob, pose_init, par, noise, with_cost, diag)
     if pose_opt is None:
         pose_opt, samples = pose_opt_n, samples_n
     return pose_opt, samples, logw, cost, cost_init, pose_opt_n, x3d_c, offset
@@ -878,8 +982,9 @@ RSLM_MAX_POINTS = 512      # epropnp_rslm_solve keeps an object's correspondence
 def rslm_solve(prob, num_proposals, num_points, num_iter, seed=0, offset=0, inds=None, rot=None, fast_mode=False,
                offset_dev=None,
                min_lm_diagonal=1e-6, max_lm_diagonal=1e32, min_relative_decrease=1e-3,
-               initial_trust_region_radius=30.0, max_trust_region_radius=1e16, eps=1e-5):
-    """The whole random-sample LM initialiser in one launch -> pose (B,pose_len), cost (B,).
+               initial_trust_region_radius=30.0, max_trust_region_radius=1e16, eps=1e-5, with_winner=False):
+    """The whole random-sample LM initialiser in one launch -> pose (B,pose_len), cost (B,) [, winner (B,) int32: the index of the
+    returned proposal; same pose and cost as without].
     `inds` (P,B,n) int64 / `rot` (P,B[,4]) inject the random draws; None draws them on the device."""
     P, n = int(num_proposals), int(num_points)
     if inds is not None:
@@ -892,6 +997,12 @@ def rslm_solve(prob, num_proposals, num_points, num_iter, seed=0, offset=0, inds
     par = _hip.LmParams(int(num_iter), int(bool(fast_mode)), min_lm_diagonal, max_lm_diagonal, min_relative_decrease,
                         initial_trust_region_radius, max_trust_region_radius, eps)
     scratch = rslm_scratch(prob, P)
+    if with_winner:
+        winner = prob.new(prob.B, dtype=torch.int32)
+        _hip.call('epropnp_rslm_solve_diag', C.byref(prob.c), C.byref(par), P, n, int(seed), int(offset), _hip.ptr(offset_dev),
+                  _hip.ptr(inds), _hip.ptr(rot), _hip.ptr(pose), _hip.ptr(cost), _hip.ptr(scratch),
+                  0 if scratch is None else scratch.numel() * 4, _hip.ptr(winner), prob.stream)
+        return pose, cost, winner
     _hip.call('epropnp_rslm_solve', C.byref(prob.c), C.byref(par), P, n, int(seed), int(offset), _hip.ptr(offset_dev),
               _hip.ptr(inds), _hip.ptr(rot), _hip.ptr(pose), _hip.ptr(cost), _hip.ptr(scratch),
               0 if scratch is None else scratch.numel() * 4, prob.stream)

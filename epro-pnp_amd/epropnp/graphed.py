@@ -76,17 +76,19 @@ class GraphedLoss:
             if getattr(layer, 'rng_counter', None) is None:
                 layer.enable_graph_safe_rng(dev)
         self.static_inputs = [t.detach().clone().requires_grad_(t.requires_grad) for t in example_inputs]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(max(1, int(warmup))):
-                self._run_once()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        for s in self.static_inputs:
-            s.grad = None
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.static_outputs = self._run_once()
+        from .functional import diagnostics
+        with diagnostics.paused():      # a captured step records no diagnostics, and neither do its warm-up runs
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                for _ in range(max(1, int(warmup))):
+                    self._run_once()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            for s in self.static_inputs:
+                s.grad = None
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.static_outputs = self._run_once()
 
     def _run_once(self):
         for s in self.static_inputs:

@@ -104,20 +104,36 @@ class LMSolver(nn.Module):
                         torch.empty((0, self.dof, self.dof), **kw) if with_pose_cov else None,
                         torch.empty((0,), **kw) if with_cost else None)
             prob = hip.problem(x3d, x2d, w2d, camera, cost_fun, self.dof)
+            sink = hip.diagnostics.sink()       # inside a `diagnostics()` block: this call's record (None outside)
+            winner = None
             if pose_init is None or force_init_solve:
                 assert self.init_solver is not None
+                if sink is not None:
+                    hip._diag.winner = None     # the initialiser leaves its winning proposal's index here
                 if pose_init is None:
                     pose_start, _, _ = self.init_solver.solve(x3d, x2d, w2d, camera, cost_fun, fast_mode=fast_mode)
+                    use_init = None
                 else:   # keep, per object, whichever of {given pose, random-sample solution} costs less
                     if cost_init is None:
                         cost_init = hip.evaluate_cost(prob, pose_init)
                     pose_start, _, cost_start = self.init_solver.solve(
                         x3d, x2d, w2d, camera, cost_fun, with_cost=True, fast_mode=fast_mode)
-                    pose_start = torch.where((cost_init < cost_start).unsqueeze(-1), pose_init, pose_start)
+                    use_init = cost_init < cost_start
+                    pose_start = torch.where(use_init.unsqueeze(-1), pose_init, pose_start)
+                if sink is not None:
+                    winner, hip._diag.winner = getattr(hip._diag, 'winner', None), None
+                    if winner is not None and use_init is not None:
+                        winner = torch.where(use_init, torch.full_like(winner, -1), winner)
             else:
                 pose_start = pose_init
-            return hip.lm_solve(prob, pose_start, self.num_iter, fast_mode=fast_mode, with_pose_cov=with_pose_cov,
-                                with_cost=with_cost, **self._lm_kwargs())
+            if sink is None:
+                return hip.lm_solve(prob, pose_start, self.num_iter, fast_mode=fast_mode, with_pose_cov=with_pose_cov,
+                                    with_cost=with_cost, **self._lm_kwargs())
+            pose_opt, pose_cov, cost, accepts = hip.lm_solve(prob, pose_start, self.num_iter, fast_mode=fast_mode,
+                                                             with_pose_cov=with_pose_cov, with_cost=with_cost,
+                                                             with_accepts=True, **self._lm_kwargs())
+            sink.records.append(hip.DiagRecord(None if fast_mode else accepts, winner))
+            return pose_opt, pose_cov, cost
 
     # ------------------------------------------------------------------------------------------------
     def gn_step(self, x3d, x2d, w2d, pose, camera, cost_fun, composite=False):
@@ -216,10 +232,13 @@ class RSLMSolver(LMSolver):
                 counter = getattr(self, 'rng_counter', None)       # device-side call counter (hipGraph replay)
                 if counter is None:
                     self._draw_calls += 1
-                pose, min_cost = hip.rslm_solve(prob, P, n, self.num_iter, self._draw_seed,
-                                                0 if counter is not None else self._draw_calls - 1, inds, rot,
-                                                fast_mode=bool(kwargs.get('fast_mode', False)), offset_dev=counter,
-                                                **self._lm_kwargs())
+                want_winner = hip.diagnostics.sink() is not None
+                pose, min_cost, *win = hip.rslm_solve(prob, P, n, self.num_iter, self._draw_seed,
+                                                      0 if counter is not None else self._draw_calls - 1, inds, rot,
+                                                      fast_mode=bool(kwargs.get('fast_mode', False)), offset_dev=counter,
+                                                      with_winner=want_winner, **self._lm_kwargs())
+                if want_winner:
+                    hip._diag.winner = win[0]
                 if counter is not None and inds is None:
                     counter.add_(1)
                 return pose, None, min_cost
@@ -232,12 +251,15 @@ class RSLMSolver(LMSolver):
             cam_rep = camera.shallow_copy().repeat_(P)
             cost_rep = cost_fun.shallow_copy().repeat_(P)
             solve_kw = {k: v for k, v in kwargs.items() if k in ('fast_mode',)}
-            pose, _, _ = LMSolver.solve(self, x3d_s.reshape(P * bs, n, 3), x2d_s.reshape(P * bs, n, 2),
-                                        w2d_s.reshape(P * bs, n, 2), cam_rep, cost_rep,
-                                        pose_init=pose0.reshape(P * bs, pose_len), **solve_kw)
+            with hip.diagnostics.paused():      # P x B sub-problem solves: not a call of the user's
+                pose, _, _ = LMSolver.solve(self, x3d_s.reshape(P * bs, n, 3), x2d_s.reshape(P * bs, n, 2),
+                                            w2d_s.reshape(P * bs, n, 2), cam_rep, cost_rep,
+                                            pose_init=pose0.reshape(P * bs, pose_len), **solve_kw)
             pose = pose.reshape(P, bs, pose_len)
             # score every proposal on the full correspondence set (cost-only sweep kernel)
             prob = hip.problem(x3d, x2d, w2d, camera, cost_fun, self.dof)
             cost = hip.evaluate_cost(prob, pose)
             min_cost, best = cost.min(dim=0)
+            if hip.diagnostics.sink() is not None:
+                hip._diag.winner = best.to(torch.int32)
             return pose[best, torch.arange(bs, device=pose.device)], None, min_cost

@@ -175,6 +175,39 @@ int epropnp_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_pa
                                 float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
                                 float* pose_samples, void* stream);
 
+/* Per-object diagnostics of the one-call forward: what a user of the reference can print between its stages -- which LM steps
+ * were accepted (levenberg_marquardt.py:227-229), which random-sample proposal won (:346-347), what the fitted proposals were and
+ * whether cholesky_wrapper fell back (epropnp.py:16-33), how degenerate the importance weights are.  Every member is optional
+ * (NULL: not wanted); all are DEVICE pointers to caller-owned, caller-allocated memory. */
+typedef struct epropnp_diag {
+  int32_t* lm_accept_mask;  /* (B,)     bit i = step i of the MAIN solve accepted, as epropnp_lm_solve's accept_mask (0 in fast_mode) */
+  int32_t* rslm_winner;     /* (B,)     init_mode 1 / 2: index in [0, rslm_proposals) of the proposal whose pose the main solve
+                                        started from; -1 where init_mode 2 kept pose_init; not written in init_mode 0            */
+  float*   proposals;       /* (B,K,40) as epropnp_amis_forward's `proposals`                                                     */
+  float*   weight_stats;    /* (B,K+3)  see epropnp_weight_stats; computed from the call's own logweights                         */
+} epropnp_diag;
+
+/* epropnp_monte_carlo_forward with diagnostics.  diag == NULL or all members NULL: exactly the launches of the plain entry.  With
+ * any member set every regular output keeps its bits (with and without the rslm / lm / split scratch buffers): lm_accept_mask and
+ * proposals are outputs the solver and sampler launches already have, weight_stats is one more launch behind the sampler, and
+ * with rslm_winner the initialiser's winner is selected by its own reduce launch (the rule of the selection folded into the LM
+ * launch, which is skipped) so that the index of the pose handed on can be reported.  Not for use inside a hipGraph capture. */
+int epropnp_monte_carlo_forward_diag(const epropnp_problem* prob, const epropnp_mc_params* par, const float* pose_init,
+                                     const float* noise, float* x3d_centered, float* offset, float* pose_init_n,
+                                     float* start_pose, float* start_cost, float* pose_opt_n, float* pose_cov, float* cost,
+                                     float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
+                                     float* pose_samples, const epropnp_diag* diag, void* stream);
+
+/* Degeneracy of the importance weights, per object.  logweights (S,B) are the samples of num_iter AMIS iterations of
+ * S / num_iter consecutive rows each; with w_j = exp(logw_j - max_j logw_j):
+ *   stats[b] = [ess, max_share, lse, mass_0 .. mass_{K-1}]      (B, 3 + num_iter)
+ *   ess = (sum w)^2 / sum w^2 (effective sample size, in [1, S]), max_share = max w / sum w, lse = max + log sum w (the number
+ *   epropnp_mc_loss_forward keeps), mass_k = share of iteration k's samples in sum w.
+ * A column that is all -inf gives ess = max_share = mass_k = 0 and lse = -inf; a column holding a NaN or +inf gives a row of NaNs.
+ * Fixed summation order, no atomics: two launches agree to the last bit.  1 <= num_iter <= 64, mc_samples a multiple of it. */
+int epropnp_weight_stats(const float* logweights, int32_t mc_samples, int32_t num_obj, int32_t num_iter, float* stats,
+                         void* stream);
+
 int epropnp_abi_version(void);
 const char* epropnp_last_error(void);
 
@@ -182,7 +215,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
@@ -417,6 +450,12 @@ int epropnp_rslm_solve(const epropnp_problem* prob, const epropnp_lm_params* lm,
                        const int64_t* inds, const float* rot, float* pose, float* cost, void* scratch,
                        uint64_t scratch_bytes, void* stream);
 uint64_t epropnp_rslm_solve_scratch_bytes(const epropnp_problem* prob, int32_t num_proposals);
+/* The same solve, reporting which proposal won: winner (B,) int32 (or NULL) = index in [0, num_proposals) of the proposal whose pose
+ * is returned (ties: as the solve breaks them).  Pose and cost are bit-identical to epropnp_rslm_solve, with and without scratch. */
+int epropnp_rslm_solve_diag(const epropnp_problem* prob, const epropnp_lm_params* lm, int32_t num_proposals,
+                            int32_t num_points, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                            const int64_t* inds, const float* rot, float* pose, float* cost, void* scratch,
+                            uint64_t scratch_bytes, int32_t* winner, void* stream);
 
 #ifdef __cplusplus
 }
