@@ -179,6 +179,20 @@ int epropnp_weight_stats(const float* logweights, int32_t mc_samples, int32_t nu
   return pnp::launch_weight_stats(logweights, mc_samples, num_obj, num_iter, stats, (hipStream_t)stream);
 }
 
+int epropnp_posterior_summary(const float* pose_samples, const float* logweights, const float* pose_ref, int32_t mc_samples,
+                              int32_t num_obj, int32_t dof, float* summary, void* stream) {
+  pnp::StageScope prof_("posterior_summary", (hipStream_t)stream);
+  return pnp::launch_posterior_summary(pose_samples, logweights, pose_ref, mc_samples, num_obj, dof, summary, (hipStream_t)stream);
+}
+
+int epropnp_posterior_resample(const float* pose_samples, const float* logweights, int32_t mc_samples, int32_t num_obj,
+                               int32_t dof, int32_t num_draws, const float* u, uint64_t seed, uint64_t offset, int32_t* index,
+                               float* poses, void* stream) {
+  pnp::StageScope prof_("posterior_resample", (hipStream_t)stream);
+  return pnp::launch_posterior_resample(pose_samples, logweights, mc_samples, num_obj, dof, num_draws, u, seed, offset, index, poses,
+                                        (hipStream_t)stream);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);

@@ -268,6 +268,11 @@ int launch_adaptive_delta(const float* x2d, const float* w2d, int B, int N, floa
                           hipStream_t st);
 int launch_mc_loss_forward(const float* logw, const float* ct, int S, int B, float* loss, float* lse, hipStream_t st);
 int launch_weight_stats(const float* logw, int S, int B, int K, float* stats, hipStream_t st);
+// posterior_kernels.hip: moments / systematic resampling of the weighted pose samples (epropnp_posterior_summary / _resample)
+int launch_posterior_summary(const float* pose, const float* logw, const float* ref, int S, int B, int dof, float* out,
+                             hipStream_t st);
+int launch_posterior_resample(const float* pose, const float* logw, int S, int B, int dof, int R, const float* u,
+                              unsigned long long seed, unsigned long long offset, int32_t* index, float* poses, hipStream_t st);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

@@ -208,6 +208,42 @@ int epropnp_monte_carlo_forward_diag(const epropnp_problem* prob, const epropnp_
 int epropnp_weight_stats(const float* logweights, int32_t mc_samples, int32_t num_obj, int32_t num_iter, float* stats,
                          void* stream);
 
+/* Posterior summary of the weighted pose samples, per object, in one launch: what the consumers of monte_carlo_forward's raw
+ * (pose_samples, pose_sample_logweights) otherwise re-derive with chains of elementwise and reduce launches over (S,B,.) temporaries
+ * -- the Det head's test-time orientation score (EPro-PnP-Det deform_pnp_head.py:532-537: softmax(dim=0) of the log-weights, norm of
+ * pose_samples[..., [0, 2]] - pose_opt[:, [0, 2]], ((-log2 + 2.5) / 4).clamp(0, 1), sum over the samples) and the moments of the
+ * distribution.  With w_j = exp(logw_j - max_j logw_j) (one rounding in the exponent's argument), W = sum w_j, t the translation
+ * (words 0..2 of a pose), samples of weight 0 skipped (a NaN pose under a -inf log-weight reaches no sum):
+ *   summary[b] (16 floats, every word written):
+ *    0..2   trans_mean = sum w t / W
+ *    3..8   upper triangle (xx, xy, xz, yy, yz, zz) of trans_cov = sum w (t - mean)(t - mean)^T / W (the definition of the
+ *           proposals' translation moments, epropnp.py:240-248), accumulated about the object's heaviest sample
+ *    9      score_te = sum w clamp((-log2 |t_xz - ref_xz| + 2.5) / 4, 0, 1) / W (deform_pnp_head.py:532-537 with pose_ref =
+ *           pose_opt; a deviation of 0 scores 1); NaN when pose_ref is NULL
+ *    10     rotation concentration: 4-DoF the mean resultant length |(sum w cos yaw, sum w sin yaw)| / W; 6-DoF the largest
+ *           eigenvalue of M = sum w q q^T / W, in [1/4, 1]
+ *    11..14 4-DoF: the circular mean atan2(sum w sin yaw, sum w cos yaw) (epropnp.py:251-257), then three zeros; 6-DoF: the unit
+ *           eigenvector of M for that eigenvalue (the antipodally symmetric mean: q and -q count alike, as for the angular
+ *           central Gaussian proposals of EProPnP6DoF), signed so that its dot with pose_ref's quaternion is >= 0, without pose_ref so that its first
+ *           non-zero component is positive
+ *    15     reserved, 0
+ * pose_samples (S,B,P), P = 4 (dof 4) | 7 (dof 6); logweights (S,B); pose_ref (B,P) or NULL.  A column that holds a NaN or +inf
+ * log-weight, or nothing but -inf, gives a row of NaNs.  The eigenvector comes from a fixed number of cyclic Jacobi sweeps; fixed
+ * summation order, no atomics: two launches agree to the last bit.  Any mc_samples >= 1.  Capturable into a hipGraph. */
+#define EPROPNP_POSTERIOR_WORDS 16
+int epropnp_posterior_summary(const float* pose_samples, const float* logweights, const float* pose_ref, int32_t mc_samples,
+                              int32_t num_obj, int32_t dof, float* summary, void* stream);
+
+/* Systematic resampling of the weighted pose samples into num_draws equally weighted draws per object, in one launch: with one
+ * uniform u_b in [0, 1) per object -- u[b], or with u == NULL the Philox4x32-10 stream of (seed, offset, b) -- draw r is the first
+ * sample, in sample order, whose running sum of w exceeds (u_b + r) / num_draws * W.
+ *   index (R,B) int32: the sample drawn, non-decreasing in r; every entry is written exactly once; samples of weight 0 are never drawn
+ *   poses (R,B,P) or NULL: pose_samples[index[r, b], b], bit for bit
+ * Bad and empty columns (as above): index -1, NaN poses.  Deterministic; capturable into a hipGraph. */
+int epropnp_posterior_resample(const float* pose_samples, const float* logweights, int32_t mc_samples, int32_t num_obj,
+                               int32_t dof, int32_t num_draws, const float* u, uint64_t seed, uint64_t offset, int32_t* index,
+                               float* poses, void* stream);
+
 int epropnp_abi_version(void);
 const char* epropnp_last_error(void);
 
@@ -215,7 +251,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
