@@ -193,6 +193,15 @@ int epropnp_posterior_resample(const float* pose_samples, const float* logweight
                                         (hipStream_t)stream);
 }
 
+int epropnp_posterior_modes(const float* pose_samples, const float* logweights, const float* bandwidth, int32_t mc_samples,
+                            int32_t num_obj, int32_t dof, float link, int32_t max_modes, float* density, int32_t* parent,
+                            int32_t* labels, int32_t* num_modes, int32_t* mode_index, float* mode_mass, float* mode_poses,
+                            void* stream) {
+  pnp::StageScope prof_("posterior_modes", (hipStream_t)stream);
+  return pnp::launch_posterior_modes(pose_samples, logweights, bandwidth, mc_samples, num_obj, dof, link, max_modes, density, parent,
+                                     labels, num_modes, mode_index, mode_mass, mode_poses, (hipStream_t)stream);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);

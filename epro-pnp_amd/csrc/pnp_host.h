@@ -273,6 +273,10 @@ int launch_posterior_summary(const float* pose, const float* logw, const float* 
                              hipStream_t st);
 int launch_posterior_resample(const float* pose, const float* logw, int S, int B, int dof, int R, const float* u,
                               unsigned long long seed, unsigned long long offset, int32_t* index, float* poses, hipStream_t st);
+// quick-shift modes of the weighted pose samples (epropnp_posterior_modes): two pair launches and a label launch
+int launch_posterior_modes(const float* pose, const float* logw, const float* bandwidth, int S, int B, int dof, float link,
+                           int max_modes, float* density, int32_t* parent, int32_t* labels, int32_t* num_modes,
+                           int32_t* mode_index, float* mode_mass, float* mode_poses, hipStream_t st);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

@@ -94,6 +94,7 @@ def _declare(lib):
     lib.epropnp_weight_stats.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.epropnp_posterior_summary.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.epropnp_posterior_resample.argtypes = [vp, vp, i32, i32, i32, i32, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
+    lib.epropnp_posterior_modes.argtypes = [vp, vp, vp, i32, i32, i32, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.epropnp_evaluate_cost.argtypes = [C.POINTER(Problem), vp, i32, vp, vp]
     lib.epropnp_normal_equations.argtypes = [C.POINTER(Problem), vp, i32, vp, vp, vp, vp]
     lib.epropnp_cost_pose_cam_grad.argtypes = [C.POINTER(Problem), vp, vp, i32, i32, vp, vp, vp]
@@ -131,7 +132,8 @@ def _declare(lib):
                  'mc_loss_forward', 'mc_loss_backward', 'rslm_draw', 'gn_step_forward', 'gn_step_backward', 'rslm_solve', 'center_points', 'shift_poses', 'prepare_forward', 'prepare_backward', 'pose_opt_plus_forward', 'pose_opt_plus_backward', 'shift_poses_backward', 'prepare_dense_forward',
                  'prepare_dense_backward', 'amis_backward_split', 'monte_carlo_forward', 'cost_pose_cam_grad', 'mc_loss_reduce',
                  'mc_loss_reduce_backward', 'plan_amis_forward', 'plan_amis_backward', 'plan_evaluate_cost',
-                 'monte_carlo_forward_diag', 'weight_stats', 'rslm_solve_diag', 'posterior_summary', 'posterior_resample'):
+                 'monte_carlo_forward_diag', 'weight_stats', 'rslm_solve_diag', 'posterior_summary', 'posterior_resample',
+                 'posterior_modes'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -149,7 +151,7 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_lm_solve_split_bytes', 'epropnp_mc_loss_reduce', 'epropnp_mc_loss_reduce_backward', 'epropnp_exchange_pack',
            'epropnp_plan_amis_forward', 'epropnp_plan_amis_backward', 'epropnp_plan_evaluate_cost',
            'epropnp_monte_carlo_forward_diag', 'epropnp_weight_stats', 'epropnp_rslm_solve_diag',
-           'epropnp_posterior_summary', 'epropnp_posterior_resample')
+           'epropnp_posterior_summary', 'epropnp_posterior_resample', 'epropnp_posterior_modes')
 
 
 def lib():

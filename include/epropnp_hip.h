@@ -244,6 +244,35 @@ int epropnp_posterior_resample(const float* pose_samples, const float* logweight
                                int32_t dof, int32_t num_draws, const float* u, uint64_t seed, uint64_t offset, int32_t* index,
                                float* poses, void* stream);
 
+/* Posterior modes: quick-shift clustering of the weighted pose samples, per object -- where the peaks of the pose distribution are,
+ * how much probability mass each holds and which samples belong to which (a symmetric object's yaw posterior has two peaks pi
+ * apart; the moments of epropnp_posterior_summary describe neither).  Per object b, all in fp32:
+ *   weights   w_j = exp(logw_j - max_j logw_j), W = sum w_j.  A sample with w_j == 0 takes no part (a NaN pose may sit there).
+ *   distance  D_ij = |t_i - t_j|^2 / h_t^2 + rho_ij / h_r^2 with (h_t, h_r) = bandwidth[b] -- "the scale below which two poses are
+ *             the same hypothesis", h_r in radians -- and rho written so that fp32 does not cancel:
+ *               4-DoF  rho = 4 sin^2((yaw_i - yaw_j) / 2)
+ *               6-DoF  d^2 = min(|q_i - q_j|^2, |q_i + q_j|^2), rho = d^2 (4 - d^2)      (= 4 (1 - (q_i . q_j)^2): q and -q count alike)
+ *   density   f_i = sum_j w_j exp(-D_ij / 2) / W over the participating j, j = i included
+ *   link      parent(i) = the participating j with (f_j > f_i or (f_j == f_i and j < i)) and D_ij <= link^2 that minimises D_ij,
+ *             ties to the lowest j, the comparison on the fp32 densities as written; no such j: i is a root, a mode
+ *   label     the root of i's chain; the mass of a mode is sum w_i / W over its tree; modes are ranked by mass, descending, ties to
+ *             the lower root index
+ * Outputs (every element of every output is written); M = max_modes:
+ *   density (S,B) f_i | parent (S,B) (a root is its own parent) | labels (S,B) the root's sample index | num_modes (B,) the number
+ *   of roots, which may exceed M | rows m < min(M, num_modes): mode_index (M,B) the root's sample index, mode_mass (M,B),
+ *   mode_poses (M,B,P) or NULL = pose_samples[mode_index, b] bit for bit; rows beyond: index -1, mass 0, NaN poses.
+ *   Samples that take no part: density NaN, parent and label -1.  A bad column -- a NaN or +inf log-weight, nothing but -inf, a
+ *   bandwidth that is not finite and > 0 -- : num_modes 0, index, parent and label -1, mass, density and poses NaN.
+ * density, parent and labels are the scratch of the call: three launches on `stream`, no allocation, no host synchronisation; sums
+ * in a fixed order, no floating-point atomics: two launches agree to the last bit.  Any mc_samples >= 1 (columns beyond 4096 samples
+ * stream through LDS in tiles).  EPROPNP_EINVAL: dof not 4 or 6, mc_samples < 1, max_modes < 1, link not finite or not > 0, a NULL
+ * pointer other than mode_poses.  num_obj == 0 launches nothing.  Capturable into a hipGraph. */
+int epropnp_posterior_modes(const float* pose_samples, const float* logweights, const float* bandwidth /* (B,2): h_t, h_r */,
+                            int32_t mc_samples, int32_t num_obj, int32_t dof, float link, int32_t max_modes,
+                            float* density /* (S,B) */, int32_t* parent /* (S,B) */, int32_t* labels /* (S,B) */,
+                            int32_t* num_modes /* (B,) */, int32_t* mode_index /* (M,B) */, float* mode_mass /* (M,B) */,
+                            float* mode_poses /* (M,B,P) or NULL */, void* stream);
+
 int epropnp_abi_version(void);
 const char* epropnp_last_error(void);
 
@@ -251,7 +280,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
