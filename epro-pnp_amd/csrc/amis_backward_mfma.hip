@@ -20,6 +20,8 @@
 //   * the VALU keeps what is genuinely per pair: perspective divide, weighted residual, Huber weight, and the
 //     accumulation of the gradients -- since round 6 on explicit 2-vectors: two point-poses per v_pk_*_f32 (22.6 wave-level
 //     instructions per pair with four resident tiles, 2 of them transcendental; the loop is bound by how often a wave gets to issue, profiles/r06_bwd_packed.txt).
+//     With the forward's sample costs at hand (DCOST below) the threshold's gradient needs no per-pair term: two clamped multiplies and
+//     a packed fma per two pairs less (profiles/bwd_dcost_bench.txt).
 // The weighted poses are built ONCE into an LDS table (compacted: the low-weight tail whose total |weight| is below
 // drop_eps -- default 2^-24 -- of the object's total is dropped before tiling, mass_drop_threshold in amis_common.h;
 // EPROPNP_BWD_DROP=0 keeps every non-zero sample), then every wave sweeps all pose tiles for its own points.
@@ -41,14 +43,25 @@ namespace pnp {
 template <int DOF, bool BOUNDS, int NPT, bool BF16>
 constexpr int bwd_min_waves() { return (NPT <= 2) ? PNP_BWD_MINW : PNP_BWD_MINW4; }
 
-template <int DOF, bool BOUNDS, int NPT, bool BF16 = false>
+// DCOST: d/d delta from the forward's sample costs instead of a per-pair term.  In the kernel's units (residuals / delta, s = |r|^2,
+// c1 = min(1, 1 / rho)) the Huber value of a sample is  cost / delta^2 = sum_n m (rho - m / 2), m = min(rho, 1)
+//                                                                     = sum_n c1 s - 1/2 sum_n min(s, 1)
+// (inlier: s / 2 = s - s / 2; outlier: rho - 1/2 = rho - 1/2), hence  sum_j a_j sum_n min(s, 1) = 2 (sum_pairs coef s - sum_j a_j cost_j / delta^2)
+// and the object's  sum_pairs coef s - sum_pairs a min(s, 1)  becomes  2 C_b - sum_pairs coef s,  C_b = sum_j a_j cost_j / delta^2:
+// S multiply-adds per object while the pose table is built, where the pair loop spent two clamped multiplies and a packed fma per two
+// pairs (`gsat2`).  cost_j is what the AMIS forward held when it wrote logweights (AmisParams.sample_costs), the cost of pose_init is
+// the forward's cost_init.  grad_delta is then a difference of two sums computed by two kernels -- equal to the per-pair form within
+// rounding, not bit for bit; the per-point gradients do not change.  Callers without costs launch the DCOST = false instantiations.
+template <int DOF, bool BOUNDS, int NPT, bool BF16 = false, bool DCOST = false>
 __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) void amis_backward_mfma_kernel(Problem p, const float* __restrict__ pose_samples,
                                                                      const float* __restrict__ g_logw, int S,
                                                                      const float* __restrict__ pose_init,
                                                                      const float* __restrict__ g_init, int P16,
                                                                      float* __restrict__ gx3d, float* __restrict__ gx2d,
                                                                      float* __restrict__ gw2d, float* __restrict__ gdelta,
-                                                                     int nsplit, float drop_eps, int gw_rows) {
+                                                                     int nsplit, float drop_eps, int gw_rows,
+                                                                     const float* __restrict__ sample_costs,
+                                                                     const float* __restrict__ cost_init) {
   constexpr int PL = PoseLen<DOF>::value;
   typedef ProjOp<BF16> Proj;      // the projection MFMA: fp32 16x16x4, or the bf16x3 split on 16x16x32 (wave_ops.h)
   // nsplit > 1 (few objects): an object's point chunks are dealt to nsplit workgroups (v = b * nsplit + part), each with
@@ -93,6 +106,30 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
   // uniform branch instead.
   const float g_init_b = with_init ? g_init[b] : 0.f;
 
+  // DCOST: the cost of pose_init in the kernel's units.  cost_init was evaluated at the caller's threshold; one that huber_scale
+  // carries as 1e-12 (delta = 0: cost_init is exactly 0 there) does not give the kernel's Huber value, so in that case -- degenerate
+  // objects -- the workgroup evaluates it here, one pass over the object's points.
+  float cinit_u = 0.f;
+  if (DCOST && with_init) {
+    if (hs.inv_delta < 1e12f) {
+      cinit_u = (cost_init[b] * hs.inv_delta) * hs.inv_delta;
+    } else {
+      float ps[PL], R[9], KR[9], Kt[3];
+#pragma unroll
+      for (int i = 0; i < PL; ++i) ps[i] = pose_init[(size_t)b * PL + i];
+      pose_to_rot<DOF>(ps, R);
+      compose_kr_kt(Kc, R, ps, KR, Kt);
+      float c[1] = {0.f};
+      for (int n = tid; n < p.N; n += T) {
+        SweepPoint q = to_sweep_point(load_point(p, b, n));
+        q.wu *= hs.inv_delta; q.wv *= hs.inv_delta; q.cu *= hs.inv_delta; q.cv *= hs.inv_delta;
+        c[0] += sweep_cost<BOUNDS>(q, KR, Kt, p.z_min, 1.0f, bd);
+      }
+      block_sum<1>(c, red);
+      cinit_u = c[0];
+    }
+  }
+
   // ---- weights, drop threshold (mass_drop_threshold, amis_common.h), compaction ----
   float amax = 0.f;
   for (int m = tid; m < P; m += T) {
@@ -133,10 +170,17 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
   // Pose table layout: [group of 4 poses][component row * 4 + k][pose in group] -- component (row, k) of (K R | K t), k = 3 the
   // translation column.  The sweep's lanes each own one group (poses g4 .. g4 + 3 of a tile): a float4 read is one component of the
   // lane's four poses, i.e. two aligned register PAIRS (poses 0, 1 | 2, 3) -- the operands of the packed pair loop below.
+  // DCOST: C_b = sum over the KEPT samples of weight x cost / delta^2 rides along -- dropped and zero-weight samples are not in idx, so
+  // their costs (possibly inf) are never read and no 0 * inf appears
+  float csum[1] = {0.f};
   for (int c = tid; c < ntile * 16; c += T) {
     float* dst = ptab + (c >> 2) * 48 + (c & 3);
     if (c < nact) {
       const int m = idx[c];
+      if (DCOST) {
+        const float cu = (m < S) ? (sample_costs[(size_t)m * p.B + b] * hs.inv_delta) * hs.inv_delta : cinit_u;
+        csum[0] = fmaf(wraw[m], cu, csum[0]);
+      }
       const float* src = (m < S) ? pose_samples + ((size_t)m * p.B + b) * PL : pose_init + (size_t)b * PL;
       float ps[PL], R[9], KR[9], Kt[3];
 #pragma unroll
@@ -156,6 +200,11 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
     }
   }
   __syncthreads();
+  float Cb = 0.f;
+  if (DCOST) {      // one block sum in a fixed order (wave_ops.h); the total is wave-uniform: kept in a scalar register across the sweep
+    block_sum<1>(csum, red);
+    Cb = bits_f32((unsigned)__builtin_amdgcn_readfirstlane((int)f32_bits(csum[0])));
+  }
   PNP_PHASE(3);
 
   const int col = lane & 15, kk = lane >> 4, g4 = kk * 4;
@@ -249,7 +298,7 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
             const f32x2 s22 = fma2(rx2, rx2, fma2(ry2, ry2, tiny2));      // |r|^2 + 1e-30: one v_max less per pair than clamping
             const f32x2 c12 = {sat_mul(fast_rsqrt(s22[0]), one_v), sat_mul(fast_rsqrt(s22[1]), one_v)};
             coef2 = aw2 * c12;
-            gsat2 = fma2(aw2, f32x2{sat_mul(s22[0], one_v), sat_mul(s22[1], one_v)}, gsat2);
+            if (!DCOST) gsat2 = fma2(aw2, f32x2{sat_mul(s22[0], one_v), sat_mul(s22[1], one_v)}, gsat2);
             crx2 = coef2 * rx2;
             cry2 = coef2 * ry2;
             ghx2 = crx2 * wrx2;
@@ -264,7 +313,7 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
             const f32x2 s22 = fma2(rx2, rx2, fma2(ry2, ry2, tiny2));
             const f32x2 c12 = {sat_mul(fast_rsqrt(s22[0]), one_v), sat_mul(fast_rsqrt(s22[1]), one_v)};
             coef2 = aw2 * c12;
-            gsat2 = fma2(aw2, f32x2{sat_mul(s22[0], one_v), sat_mul(s22[1], one_v)}, gsat2);
+            if (!DCOST) gsat2 = fma2(aw2, f32x2{sat_mul(s22[0], one_v), sat_mul(s22[1], one_v)}, gsat2);
             crx2 = coef2 * rx2;
             cry2 = coef2 * ry2;
             f32x2 gpx2 = crx2 * wu2, gpy2 = cry2 * wv2;
@@ -296,10 +345,11 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
     }
     const float gsat = gsat2[0] + gsat2[1];
     {   // d/d delta of this chunk: sum_pairs coef |r|^2 (= the sums behind d/dw, before their per-point factors) - sum_pairs a min(|r|^2, 1)
+        // (DCOST: 2 C_b - sum_pairs coef |r|^2, the object's C_b added once behind the chunk loop)
       float a2 = 0.f;
 #pragma unroll
       for (int i = 0; i < NPT; ++i) a2 += (A2x[i][0] + A2x[i][1]) + (A2y[i][0] + A2y[i][1]);
-      gd += a2 - gsat;
+      gd += DCOST ? -a2 : a2 - gsat;
     }
     // ---- outputs of this chunk: sums over the 4 pose groups of a point via MFMAs against indicator columns ----
     // The lane geometry is re-derived here behind an opaque copy of the lane index: as invariants of the chunk loop the four
@@ -338,6 +388,7 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
     }
   }
   PNP_PHASE(4);
+  if (DCOST && part == 0 && tid == 0) gd += 2.0f * Cb;      // (split launch: the partials of the other parts stay partials)
   float one[1] = {gd * hs.delta};
   block_sum<1>(one, red);
   if (tid == 0) gdelta[v] = one[0];
@@ -435,10 +486,17 @@ int plan_amis_backward_record(const epropnp_problem* prob, int mc_samples, int w
 // returns 1 when the shape is not supported (caller falls back to amis_backward_kernel)
 int launch_amis_backward_mfma(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
                               int mc_samples, const float* pose_init, const float* grad_cost_init, float* grad_x3d,
-                              float* grad_x2d, float* grad_w2d, float* grad_delta, int nsplit, hipStream_t st) {
+                              float* grad_x2d, float* grad_w2d, float* grad_delta, int nsplit, hipStream_t st,
+                              const float* sample_costs, const float* cost_init) {
   const Problem d = to_device_problem(prob);
   BwdPlan plan;
-  if (plan_amis_backward(prob, mc_samples, pose_init && grad_cost_init, nsplit, &plan)) return 1;
+  const bool with_init = pose_init && grad_cost_init;
+  if (plan_amis_backward(prob, mc_samples, with_init, nsplit, &plan)) return 1;
+  // d/d delta from the forward's costs (kernel comment: DCOST) when the caller hands them over -- the costs of the samples and, with a
+  // pose_init term, cost_init; otherwise the per-pair instantiation, to the bits of the entries without costs.  The launch shape is
+  // the plan's either way.  EPROPNP_TUNE=bwd_dcost=0 keeps the per-pair path (A/B).
+  bool dcost = sample_costs != nullptr && mc_samples > 0 && (!with_init || cost_init != nullptr);
+  { int ov[1]; if (tune_ints("bwd_dcost", ov, 1) && ov[0] == 0) dcost = false; }
   const int waves = plan.waves, npt = plan.npt, P16 = plan.P16, gw_rows = plan.gw_rows;
   const size_t smem = plan.smem;
   const bool bf16 = plan.bf16;
@@ -447,15 +505,16 @@ int launch_amis_backward_mfma(const epropnp_problem* prob, const float* pose_sam
     auto launch = [&](auto kern) -> int {
       allow_dynamic_lds((const void*)kern, smem);
       PNP_LAUNCH(kern, grid, block, smem, st, d, pose_samples, grad_logweights, mc_samples, pose_init, grad_cost_init, P16,
-                 grad_x3d, grad_x2d, grad_w2d, grad_delta, nsplit, backward_drop_eps(), gw_rows);
+                 grad_x3d, grad_x2d, grad_w2d, grad_delta, nsplit, backward_drop_eps(), gw_rows, sample_costs, cost_init);
       return 0;
     };
-    if (bf16)
-      return (npt == 1)   ? launch(amis_backward_mfma_kernel<decltype(DOF)::value, decltype(BND)::value, 1, true>)
-             : (npt == 2) ? launch(amis_backward_mfma_kernel<decltype(DOF)::value, decltype(BND)::value, 2, true>)
-                          : launch(amis_backward_mfma_kernel<decltype(DOF)::value, decltype(BND)::value, 4, true>);
     return dispatch_bwd_npt(npt, [&](auto NPT) -> int {
-      return launch(amis_backward_mfma_kernel<decltype(DOF)::value, decltype(BND)::value, decltype(NPT)::value>);
+      constexpr int kDof = decltype(DOF)::value, kNpt = decltype(NPT)::value;
+      constexpr bool kBnd = decltype(BND)::value;
+      if (dcost)
+        return bf16 ? launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true, true>)
+                    : launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, false, true>);
+      return bf16 ? launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true>) : launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, false>);
     });
   });
   return check_launch("amis_backward_mfma_kernel");

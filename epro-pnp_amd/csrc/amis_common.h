@@ -80,6 +80,9 @@ struct AmisParams {
   const float* dn_offset;   // (B,3) object centres, or nullptr
   float* dn_samples;        // (S,B,PL)
   float* dn_pose_opt;       // (B,PL)
+  // optional (S,B), the layout of logweights: the Huber cost of every sample, which logw = -cost - (mix - log n) discards -- the
+  // backward takes the threshold's gradient from it (epropnp_amis_backward_costs, include/epropnp_hip.h)
+  float* sample_costs;
 };
 
 // pnp_denormalize of pose_opt (AmisParams.dn_*): one thread of the object's (first) workgroup

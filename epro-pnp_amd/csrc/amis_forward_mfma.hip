@@ -399,6 +399,7 @@ __global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PN
     for (int m = tid; m < S; m += T) {
       const float lw = lgw[m];
       logweights[(size_t)m * p.B + b] = lw;
+      if (a.sample_costs != nullptr) a.sample_costs[(size_t)m * p.B + b] = cst[m];
       st_bits |= (lw == lw && lw != INFINITY) ? 0 : EPROPNP_ST_NONFINITE_WEIGHT;     // -inf = zero weight is legitimate
     }
     for (int i = tid; i < K; i += T)
@@ -575,7 +576,7 @@ int plan_amis_forward_record(const epropnp_problem* prob, int S, int K, unsigned
 
 int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_params* am, const float* pose_opt,
                              const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
-                             float* proposals, hipStream_t st, const DenormOut* dn) {
+                             float* proposals, hipStream_t st, const DenormOut* dn, float* sample_costs) {
   const Problem d = to_device_problem(prob);
   const int S = am->mc_samples, K = am->num_iter;
   const int PL = prob->dof == 6 ? 7 : 4;
@@ -592,6 +593,7 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
   k.advance_ticket = (int*)am->advance_ticket; k.advance_count = am->advance_count;
   k.split_timeout = split_timeout_cycles();
   k.dn_offset = dn ? dn->offset : nullptr; k.dn_samples = dn ? dn->samples : nullptr; k.dn_pose_opt = dn ? dn->pose_opt : nullptr;
+  k.sample_costs = sample_costs;
   { int ab[1]; if (tune_ints("ablate", ab, 1)) k.ablate = ab[0]; }
   float* spill = nullptr;
   if (plan.spilled &&

@@ -132,6 +132,7 @@ __global__ __launch_bounds__(MAXW * 64, (MAXW == 4 ? (PPL >= 8 ? 2 : 3) : 1)) vo
     for (int m = tid; m < S; m += T) {
       const float lw = lgw[m];
       logweights[(size_t)m * p.B + b] = lw;
+      if (a.sample_costs != nullptr) a.sample_costs[(size_t)m * p.B + b] = cst[m];
       st_bits |= (lw == lw && lw != INFINITY) ? 0 : EPROPNP_ST_NONFINITE_WEIGHT;     // -inf = zero weight is legitimate
     }
     for (int i = tid; i < K; i += T)
@@ -301,7 +302,7 @@ __global__ __launch_bounds__(MAXW * 64, (MAXW == 4 ? (PPL >= 8 ? 2 : (PPL == 4 ?
 // ================================================================================================================
 int launch_amis_forward(const epropnp_problem* prob, const epropnp_amis_params* am, const float* pose_opt,
                         const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
-                        float* proposals, hipStream_t st, const DenormOut* dn) {
+                        float* proposals, hipStream_t st, const DenormOut* dn, float* sample_costs) {
   if (int rc = check_problem(prob)) return rc;
   if (!am) return fail(EPROPNP_EINVAL, "amis_forward: params NULL");
   if (am->num_iter <= 0 || am->mc_samples <= 0 || am->mc_samples % am->num_iter != 0)
@@ -312,7 +313,7 @@ int launch_amis_forward(const epropnp_problem* prob, const epropnp_amis_params* 
   {   // default: projection on the matrix cores (amis_forward_mfma.hip); EPROPNP_TUNE="fwd_impl=valu" keeps the VALU sweep
     const char* impl = tune_value("fwd_impl");
     if (!(impl && impl[0] == 'v'))
-      return launch_amis_forward_mfma(prob, am, pose_opt, pose_cov, noise, pose_samples, logweights, proposals, st, dn);
+      return launch_amis_forward_mfma(prob, am, pose_opt, pose_cov, noise, pose_samples, logweights, proposals, st, dn, sample_costs);
   }
   if (prob->num_pts > kMaxResidentPoints)
     return fail(EPROPNP_EINVAL, "amis_forward: num_pts %d exceeds the register-resident limit %d", prob->num_pts,
@@ -346,6 +347,7 @@ int launch_amis_forward(const epropnp_problem* prob, const epropnp_amis_params* 
   k.advance_ticket = (int*)am->advance_ticket; k.advance_count = am->advance_count;
   k.ablate = 0;
   k.dn_offset = dn ? dn->offset : nullptr; k.dn_samples = dn ? dn->samples : nullptr; k.dn_pose_opt = dn ? dn->pose_opt : nullptr;
+  k.sample_costs = sample_costs;
   { int ab[1]; if (tune_ints("ablate", ab, 1)) k.ablate = ab[0]; }
   // the float4-viewed arrays (ptab rows, wred) come first so that they are 16-B aligned for any S
   const size_t smem = sizeof(float) * (12 * (size_t)s + (size_t)PL * S + 3 * (size_t)S + (size_t)WP * s +
@@ -392,7 +394,8 @@ int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int npar
 // caller to add in a fixed order (no atomics: results stay reproducible).
 int launch_amis_backward_split(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
                                int mc_samples, const float* pose_init, const float* grad_cost_init, int nsplit,
-                               float* grad_x3d, float* grad_x2d, float* grad_w2d, float* grad_delta_parts, hipStream_t st) {
+                               float* grad_x3d, float* grad_x2d, float* grad_w2d, float* grad_delta_parts, hipStream_t st,
+                               const float* sample_costs, const float* cost_init) {
   if (int rc = check_problem(prob)) return rc;
   if (prob->num_obj == 0 || prob->num_pts == 0) return EPROPNP_OK;
   if (mc_samples < 0) return fail(EPROPNP_EINVAL, "amis_backward_split: negative mc_samples");
@@ -401,7 +404,7 @@ int launch_amis_backward_split(const epropnp_problem* prob, const float* pose_sa
   if (nsplit < 1 || nsplit > 16 || (long long)nsplit * 64 > (long long)((prob->num_pts + 63) / 64) * 64)
     return fail(EPROPNP_EINVAL, "amis_backward_split: nsplit %d not in [1, min(16, ceil(num_pts / 64))]", nsplit);
   const int rc = launch_amis_backward_mfma(prob, pose_samples, grad_logweights, mc_samples, pose_init, grad_cost_init,
-                                           grad_x3d, grad_x2d, grad_w2d, grad_delta_parts, nsplit, st);
+                                           grad_x3d, grad_x2d, grad_w2d, grad_delta_parts, nsplit, st, sample_costs, cost_init);
   if (rc == 1) return fail(EPROPNP_EINVAL, "amis_backward_split: mc_samples %d does not fit the LDS pose table", mc_samples);
   if (rc != 0) return rc;
   return nsplit > 1 ? launch_delta_path(prob, grad_delta_parts, nsplit, grad_w2d, st) : EPROPNP_OK;      // (1 part: the kernel's epilogue)
@@ -409,7 +412,8 @@ int launch_amis_backward_split(const epropnp_problem* prob, const float* pose_sa
 
 int launch_amis_backward(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
                          int mc_samples, const float* pose_init, const float* grad_cost_init, float* grad_x3d,
-                         float* grad_x2d, float* grad_w2d, float* grad_delta, hipStream_t st) {
+                         float* grad_x2d, float* grad_w2d, float* grad_delta, hipStream_t st, const float* sample_costs,
+                         const float* cost_init) {
   if (int rc = check_problem(prob)) return rc;
   if (prob->num_obj == 0 || prob->num_pts == 0) return EPROPNP_OK;
   if (mc_samples < 0) return fail(EPROPNP_EINVAL, "amis_backward: negative mc_samples");
@@ -419,7 +423,7 @@ int launch_amis_backward(const epropnp_problem* prob, const float* pose_samples,
       // EPROPNP_TUNE="bwd_impl=valu" forces this file's all-VALU kernel
     if (!backward_valu_forced()) {
       const int rc = launch_amis_backward_mfma(prob, pose_samples, grad_logweights, mc_samples, pose_init, grad_cost_init,
-                                               grad_x3d, grad_x2d, grad_w2d, grad_delta, 1, st);
+                                               grad_x3d, grad_x2d, grad_w2d, grad_delta, 1, st, sample_costs, cost_init);
       if (rc <= 0) return rc;     // 1 = shape not supported there (pose table larger than LDS)
     }
   }

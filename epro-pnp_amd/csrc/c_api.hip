@@ -94,7 +94,23 @@ int32_t* default_status_word() {
 }
 }  // namespace pnp
 
+namespace pnp {
+// epropnp_request_sample_costs: where the next forward entry of this host thread stores its samples' costs; taken (and forgotten)
+// by that call whatever it returns
+static thread_local float* g_requested_costs = nullptr;
+static float* take_requested_costs() {
+  float* p = g_requested_costs;
+  g_requested_costs = nullptr;
+  return p;
+}
+}  // namespace pnp
+
 extern "C" {
+
+int epropnp_request_sample_costs(float* sample_costs) {
+  pnp::g_requested_costs = sample_costs;
+  return EPROPNP_OK;
+}
 
 int32_t* epropnp_async_status_word(void) { return pnp::default_status_word(); }
 
@@ -160,7 +176,7 @@ int epropnp_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_pa
                                 float* pose_samples, void* stream) {
   return pnp::launch_monte_carlo_forward(prob, par, pose_init, noise, x3d_centered, offset, pose_init_n, start_pose,
                                          start_cost, pose_opt_n, pose_cov, cost, pose_samples_n, logweights, cost_init,
-                                         pose_opt, pose_samples, (hipStream_t)stream);
+                                         pose_opt, pose_samples, (hipStream_t)stream, nullptr, pnp::take_requested_costs());
 }
 
 int epropnp_monte_carlo_forward_diag(const epropnp_problem* prob, const epropnp_mc_params* par, const float* pose_init,
@@ -170,7 +186,7 @@ int epropnp_monte_carlo_forward_diag(const epropnp_problem* prob, const epropnp_
                                      float* pose_samples, const epropnp_diag* diag, void* stream) {
   return pnp::launch_monte_carlo_forward(prob, par, pose_init, noise, x3d_centered, offset, pose_init_n, start_pose,
                                          start_cost, pose_opt_n, pose_cov, cost, pose_samples_n, logweights, cost_init,
-                                         pose_opt, pose_samples, (hipStream_t)stream, diag);
+                                         pose_opt, pose_samples, (hipStream_t)stream, diag, pnp::take_requested_costs());
 }
 
 int epropnp_weight_stats(const float* logweights, int32_t mc_samples, int32_t num_obj, int32_t num_iter, float* stats,
@@ -236,7 +252,7 @@ int epropnp_amis_forward(const epropnp_problem* prob, const epropnp_amis_params*
                          float* proposals, void* stream) {
   pnp::StageScope prof_("amis_forward", (hipStream_t)stream);
   return pnp::launch_amis_forward(prob, amis, pose_opt, pose_cov, noise, pose_samples, logweights, proposals,
-                                  (hipStream_t)stream);
+                                  (hipStream_t)stream, nullptr, pnp::take_requested_costs());
 }
 
 int epropnp_amis_backward(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
@@ -255,6 +271,44 @@ int epropnp_amis_backward_split(const epropnp_problem* prob, const float* pose_s
                                          num_split, grad_x3d, grad_x2d, grad_w2d, grad_delta_parts, (hipStream_t)stream);
 }
 
+int epropnp_amis_forward_costs(const epropnp_problem* prob, const epropnp_amis_params* amis, const float* pose_opt,
+                               const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
+                               float* proposals, float* sample_costs, void* stream) {
+  (void)pnp::take_requested_costs();      // (an explicit output: a pending request is dropped, not carried to a later call)
+  pnp::StageScope prof_("amis_forward", (hipStream_t)stream);
+  return pnp::launch_amis_forward(prob, amis, pose_opt, pose_cov, noise, pose_samples, logweights, proposals,
+                                  (hipStream_t)stream, nullptr, sample_costs);
+}
+
+int epropnp_monte_carlo_forward_costs(const epropnp_problem* prob, const epropnp_mc_params* par, const float* pose_init,
+                                      const float* noise, float* x3d_centered, float* offset, float* pose_init_n,
+                                      float* start_pose, float* start_cost, float* pose_opt_n, float* pose_cov, float* cost,
+                                      float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
+                                      float* pose_samples, const epropnp_diag* diag, float* sample_costs, void* stream) {
+  (void)pnp::take_requested_costs();
+  return pnp::launch_monte_carlo_forward(prob, par, pose_init, noise, x3d_centered, offset, pose_init_n, start_pose,
+                                         start_cost, pose_opt_n, pose_cov, cost, pose_samples_n, logweights, cost_init,
+                                         pose_opt, pose_samples, (hipStream_t)stream, diag, sample_costs);
+}
+
+int epropnp_amis_backward_costs(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
+                                int32_t mc_samples, const float* pose_init, const float* grad_cost_init,
+                                const float* sample_costs, const float* cost_init, float* grad_x3d, float* grad_x2d,
+                                float* grad_w2d, float* grad_delta, void* stream) {
+  pnp::StageScope prof_("amis_backward", (hipStream_t)stream);
+  return pnp::launch_amis_backward(prob, pose_samples, grad_logweights, mc_samples, pose_init, grad_cost_init, grad_x3d,
+                                   grad_x2d, grad_w2d, grad_delta, (hipStream_t)stream, sample_costs, cost_init);
+}
+
+int epropnp_amis_backward_split_costs(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
+                                      int32_t mc_samples, const float* pose_init, const float* grad_cost_init, int32_t num_split,
+                                      const float* sample_costs, const float* cost_init, float* grad_x3d, float* grad_x2d,
+                                      float* grad_w2d, float* grad_delta_parts, void* stream) {
+  pnp::StageScope prof_("amis_backward", (hipStream_t)stream);
+  return pnp::launch_amis_backward_split(prob, pose_samples, grad_logweights, mc_samples, pose_init, grad_cost_init,
+                                         num_split, grad_x3d, grad_x2d, grad_w2d, grad_delta_parts, (hipStream_t)stream,
+                                         sample_costs, cost_init);
+}
 
 int epropnp_adaptive_delta(const float* x2d, const float* w2d, int32_t num_obj, int32_t num_pts, float relative_delta,
                            float* delta, float* stats, void* stream) {

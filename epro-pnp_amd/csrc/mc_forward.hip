@@ -46,7 +46,7 @@ int launch_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_par
                                const float* noise, float* x3d_centered, float* offset, float* pose_init_n,
                                float* start_pose, float* start_cost, float* pose_opt_n, float* pose_cov, float* cost,
                                float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
-                               float* pose_samples, hipStream_t st, const epropnp_diag* diag) {
+                               float* pose_samples, hipStream_t st, const epropnp_diag* diag, float* sample_costs) {
   // diagnostics (include/epropnp_hip.h: epropnp_diag); all NULL = the plain call, launch for launch
   int32_t* const d_accept = diag ? diag->lm_accept_mask : nullptr;
   int32_t* const d_winner = (diag && par && par->init_mode != 0) ? diag->rslm_winner : nullptr;
@@ -137,7 +137,8 @@ int launch_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_par
   {
     const DenormOut dn = {offset, pose_samples, pose_opt};
     StageScope ps("amis_forward", st);
-    if ((rc = launch_amis_forward(&q, &par->amis, pose_opt_n, pose_cov, noise, pose_samples_n, logweights, d_props, st, fold ? &dn : nullptr)))
+    if ((rc = launch_amis_forward(&q, &par->amis, pose_opt_n, pose_cov, noise, pose_samples_n, logweights, d_props, st, fold ? &dn : nullptr,
+                                  sample_costs)))
       return rc;
   }
   if (d_wstats) {

@@ -216,7 +216,8 @@ int launch_monte_carlo_forward(const epropnp_problem* prob, const epropnp_mc_par
                                const float* noise, float* x3d_centered, float* offset, float* pose_init_n,
                                float* start_pose, float* start_cost, float* pose_opt_n, float* pose_cov, float* cost,
                                float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
-                               float* pose_samples, hipStream_t st, const epropnp_diag* diag = nullptr);
+                               float* pose_samples, hipStream_t st, const epropnp_diag* diag = nullptr,
+                               float* sample_costs = nullptr);
 unsigned long long amis_forward_split_bytes(const epropnp_problem* prob, int mc_samples, int num_iter);
 // launch plans as int records (include/epropnp_hip.h: epropnp_plan_*): host only, nothing is launched
 int plan_amis_forward_record(const epropnp_problem* prob, int S, int K, unsigned long long scratch_bytes, int32_t* out);
@@ -228,7 +229,8 @@ int launch_normal_equations(const epropnp_problem* prob, const float* pose, int 
                             float* cost, hipStream_t st);
 int launch_amis_backward_mfma(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
                               int mc_samples, const float* pose_init, const float* grad_cost_init, float* grad_x3d,
-                              float* grad_x2d, float* grad_w2d, float* grad_delta, int nsplit, hipStream_t st);
+                              float* grad_x2d, float* grad_w2d, float* grad_delta, int nsplit, hipStream_t st,
+                              const float* sample_costs = nullptr, const float* cost_init = nullptr);
 int launch_rslm_solve(const epropnp_problem* prob, const epropnp_lm_params* lm, int P, int n_pts, unsigned long long seed,
                       unsigned long long offset, const unsigned long long* offset_dev, const long long* inds, const float* rot,
                       float* pose_out, float* cost_out, void* scratch, unsigned long long scratch_bytes,
@@ -309,15 +311,17 @@ unsigned long long lm_split_bytes(const epropnp_problem* prob, const epropnp_lm_
 struct DenormOut { const float* offset; float* samples; float* pose_opt; };
 int launch_amis_forward(const epropnp_problem* prob, const epropnp_amis_params* amis, const float* pose_opt,
                         const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
-                        float* proposals, hipStream_t st, const DenormOut* dn = nullptr);
+                        float* proposals, hipStream_t st, const DenormOut* dn = nullptr, float* sample_costs = nullptr);
 int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_params* amis, const float* pose_opt,
                              const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
-                             float* proposals, hipStream_t st, const DenormOut* dn = nullptr);
+                             float* proposals, hipStream_t st, const DenormOut* dn = nullptr, float* sample_costs = nullptr);
 int launch_amis_backward_split(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
                                int mc_samples, const float* pose_init, const float* grad_cost_init, int nsplit,
-                               float* grad_x3d, float* grad_x2d, float* grad_w2d, float* grad_delta_parts, hipStream_t st);
+                               float* grad_x3d, float* grad_x2d, float* grad_w2d, float* grad_delta_parts, hipStream_t st,
+                               const float* sample_costs = nullptr, const float* cost_init = nullptr);
 int launch_amis_backward(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
                          int mc_samples, const float* pose_init, const float* grad_cost_init, float* grad_x3d,
-                         float* grad_x2d, float* grad_w2d, float* grad_delta, hipStream_t st);
+                         float* grad_x2d, float* grad_w2d, float* grad_delta, hipStream_t st,
+                         const float* sample_costs = nullptr, const float* cost_init = nullptr);
 
 }  // namespace pnp

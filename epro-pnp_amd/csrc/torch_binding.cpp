@@ -169,24 +169,28 @@ struct ProblemTensors {      // contiguous fp32 device tensors behind an epropnp
   }
 };
 
+// costs (S,B) / cost_init (B,): the forward's sample costs and its cost of pose_init -- the threshold's gradient is taken from them
+// (include/epropnp_hip.h); undefined tensors = the entries without costs
 int backward_launch(const epropnp_problem& q, const Tensor& samples, const Tensor& glw, const Tensor& pin, const Tensor& gin,
-                    int64_t nsplit, Tensor& gx3d, Tensor& gx2d, Tensor& gw2d, Tensor& gdel, int64_t stream) {
+                    int64_t nsplit, Tensor& gx3d, Tensor& gx2d, Tensor& gw2d, Tensor& gdel, int64_t stream,
+                    const Tensor& costs = Tensor(), const Tensor& cost_init = Tensor()) {
   const int64_t B = q.num_obj, N = q.num_pts, S = samples.size(0);
   gx3d = torch::empty({B, N, 3}, samples.options());
   gx2d = torch::empty({B, N, 2}, samples.options());
   gw2d = torch::empty({B, N, 2}, samples.options());
   if (nsplit > 1) {
     Tensor parts = torch::empty({B, nsplit}, samples.options());
-    const int rc = epropnp_amis_backward_split(&q, fptr(samples), fptr(glw), (int32_t)S, fptr(pin), fptr(gin), (int32_t)nsplit,
-                                               fptr(gx3d), fptr(gx2d), fptr(gw2d), fptr(parts), (void*)stream);
+    const int rc = epropnp_amis_backward_split_costs(&q, fptr(samples), fptr(glw), (int32_t)S, fptr(pin), fptr(gin), (int32_t)nsplit,
+                                                     fptr(costs), fptr(cost_init), fptr(gx3d), fptr(gx2d), fptr(gw2d), fptr(parts),
+                                                     (void*)stream);
     // (the per-workgroup partials are only added up for a caller that wants d/d delta: with the threshold's gradient folded into
     // grad_w2d -- q.delta_stats -- nobody does, and the sum would be one more launch of a launch-bound step)
     if (q.delta_stats == nullptr) gdel = parts.sum(1);
     return rc;
   }
   gdel = torch::empty({B}, samples.options());
-  return epropnp_amis_backward(&q, fptr(samples), fptr(glw), (int32_t)S, fptr(pin), fptr(gin), fptr(gx3d), fptr(gx2d),
-                               fptr(gw2d), fptr(gdel), (void*)stream);
+  return epropnp_amis_backward_costs(&q, fptr(samples), fptr(glw), (int32_t)S, fptr(pin), fptr(gin), fptr(costs), fptr(cost_init),
+                                     fptr(gx3d), fptr(gx2d), fptr(gw2d), fptr(gdel), (void*)stream);
 }
 
 struct FusedMonteCarlo : public torch::autograd::Function<FusedMonteCarlo> {
@@ -227,12 +231,15 @@ struct FusedMonteCarlo : public torch::autograd::Function<FusedMonteCarlo> {
     Tensor samples_n = torch::empty({S, B, PL}, opt), logw = torch::empty({S, B}, opt);
     if (with_cost) cost = torch::empty({B}, opt);
     if (pin.defined()) cost_init = torch::empty({B}, opt);
-    check(epropnp_monte_carlo_forward(&prob, &par, fptr(pin), fptr(nz), fptr(x3d_ctr), fptr(offset), fptr(pin_n),
-                                      fptr(start_pose), fptr(start_cost), fptr(pose_opt_n), fptr(pose_cov), fptr(cost),
-                                      fptr(samples_n), fptr(logw), fptr(cost_init), fptr(pose_opt), fptr(samples),
-                                      (void*)stream), "epropnp_monte_carlo_forward");
-    // ---- what the recompute backward needs: the problem in the solver frame, the samples, pose_init in that frame
-    ctx->save_for_backward({samples_n});
+    Tensor costs = torch::empty({S, B}, opt);      // the samples' Huber costs: the backward's threshold gradient
+    check(epropnp_monte_carlo_forward_costs(&prob, &par, fptr(pin), fptr(nz), fptr(x3d_ctr), fptr(offset), fptr(pin_n),
+                                            fptr(start_pose), fptr(start_cost), fptr(pose_opt_n), fptr(pose_cov), fptr(cost),
+                                            fptr(samples_n), fptr(logw), fptr(cost_init), fptr(pose_opt), fptr(samples),
+                                            nullptr, fptr(costs), (void*)stream), "epropnp_monte_carlo_forward");
+    // ---- what the recompute backward needs: the problem in the solver frame, the samples (and their costs), pose_init in that frame
+    ctx->save_for_backward({samples_n, costs});
+    // (the forward's cost of pose_init, detached: an OUTPUT of this node must not be saved as it is -- it would own the node)
+    ctx->saved_data["cost_init"] = cost_init.defined() ? c10::IValue(cost_init.detach()) : c10::IValue();
     ctx->saved_data["x3d"] = normalize ? x3d_ctr : x3d_c;
     ctx->saved_data["x2d"] = x2d_c; ctx->saved_data["w2d"] = w2d_c; ctx->saved_data["cam"] = cam_c;
     ctx->saved_data["delta"] = delta_c;
@@ -286,14 +293,16 @@ struct FusedMonteCarlo : public torch::autograd::Function<FusedMonteCarlo> {
                     "(EPro-PnP recomputes its backward from x3d / x2d / w2d / delta / cam_mats: they must stay unchanged "
                     "between forward and backward)");
     }
-    const Tensor samples_n = ctx->get_saved_variables()[0];
+    const auto saved = ctx->get_saved_variables();
+    const Tensor samples_n = saved[0], costs = saved[1];
     const epropnp_problem q = pt.c();
     Tensor glw = g_logw_in.defined() ? g_logw_in.contiguous() : torch::full({samples_n.size(0), samples_n.size(1)}, 0.0, samples_n.options());   // (a fill kernel; zeros() is a memset node under capture)
     Tensor pin, gin;
     if (g_ci.defined() && !ctx->saved_data["pin"].isNone()) { pin = ctx->saved_data["pin"].toTensor(); gin = g_ci.contiguous(); }
-    Tensor gx3d, gx2d, gw2d, gdel;
+    Tensor gx3d, gx2d, gw2d, gdel, cinit;
+    if (!ctx->saved_data["cost_init"].isNone()) cinit = ctx->saved_data["cost_init"].toTensor();
     check(backward_launch(q, samples_n, glw, pin, gin, ctx->saved_data["nsplit"].toInt(), gx3d, gx2d, gw2d, gdel,
-                          ctx->saved_data["stream"].toInt()), "epropnp_amis_backward");
+                          ctx->saved_data["stream"].toInt(), costs, cinit), "epropnp_amis_backward");
     if (ctx->needs_input_grad(0)) out[0] = gx3d;
     if (ctx->needs_input_grad(1)) out[1] = gx2d;
     if (ctx->needs_input_grad(2)) out[2] = gw2d;

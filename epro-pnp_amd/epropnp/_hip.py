@@ -104,6 +104,13 @@ def _declare(lib):
     lib.epropnp_amis_forward.argtypes = [C.POINTER(Problem), C.POINTER(AmisParams), vp, vp, vp, vp, vp, vp, vp]
     lib.epropnp_amis_backward.argtypes = [C.POINTER(Problem), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.epropnp_amis_backward_split.argtypes = [C.POINTER(Problem), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    # the same entries with the samples' Huber costs as one more output / input (include/epropnp_hip.h: the threshold's gradient
+    # from the forward's sample costs)
+    lib.epropnp_amis_forward_costs.argtypes = [C.POINTER(Problem), C.POINTER(AmisParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.epropnp_monte_carlo_forward_costs.argtypes = [C.POINTER(Problem), C.POINTER(McParams)] + [vp] * 15 + [C.POINTER(Diag), vp, vp]
+    lib.epropnp_request_sample_costs.argtypes = [vp]
+    lib.epropnp_amis_backward_costs.argtypes = [C.POINTER(Problem), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.epropnp_amis_backward_split_costs.argtypes = [C.POINTER(Problem), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.epropnp_gn_step_forward.argtypes = [C.POINTER(Problem), C.c_float, vp, vp, vp]
     lib.epropnp_gn_step_backward.argtypes = [C.POINTER(Problem), C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.epropnp_pose_opt_plus_forward.argtypes = [C.POINTER(Problem), C.c_float, vp, vp, vp]
@@ -133,7 +140,8 @@ def _declare(lib):
                  'prepare_dense_backward', 'amis_backward_split', 'monte_carlo_forward', 'cost_pose_cam_grad', 'mc_loss_reduce',
                  'mc_loss_reduce_backward', 'plan_amis_forward', 'plan_amis_backward', 'plan_evaluate_cost',
                  'monte_carlo_forward_diag', 'weight_stats', 'rslm_solve_diag', 'posterior_summary', 'posterior_resample',
-                 'posterior_modes'):
+                 'posterior_modes', 'amis_forward_costs', 'monte_carlo_forward_costs', 'amis_backward_costs',
+                 'amis_backward_split_costs', 'request_sample_costs'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -151,7 +159,9 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_lm_solve_split_bytes', 'epropnp_mc_loss_reduce', 'epropnp_mc_loss_reduce_backward', 'epropnp_exchange_pack',
            'epropnp_plan_amis_forward', 'epropnp_plan_amis_backward', 'epropnp_plan_evaluate_cost',
            'epropnp_monte_carlo_forward_diag', 'epropnp_weight_stats', 'epropnp_rslm_solve_diag',
-           'epropnp_posterior_summary', 'epropnp_posterior_resample', 'epropnp_posterior_modes')
+           'epropnp_posterior_summary', 'epropnp_posterior_resample', 'epropnp_posterior_modes',
+           'epropnp_amis_forward_costs', 'epropnp_monte_carlo_forward_costs', 'epropnp_amis_backward_costs',
+           'epropnp_amis_backward_split_costs', 'epropnp_request_sample_costs')
 
 
 def lib():

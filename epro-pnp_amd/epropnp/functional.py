@@ -471,8 +471,10 @@ def _amis_struct(prob, S, K, eps, acg_mle_iter, acg_dispersion, seed, offset, of
 
 
 def amis_forward(prob, pose_opt, pose_cov, mc_samples, num_iter, eps=1e-5, acg_mle_iter=3, acg_dispersion=0.001,
-                 noise=None, seed=0, offset=0, with_proposals=False, offset_dev=None):
-    """-> pose_samples (S,B,pose_len), logweights (S,B) [, proposals (B,K,40)]."""
+                 noise=None, seed=0, offset=0, with_proposals=False, offset_dev=None, with_costs=False):
+    """-> pose_samples (S,B,pose_len), logweights (S,B) [, proposals (B,K,40)] [, sample_costs (S,B)].
+    with_costs: also the Huber cost of every sample (logw = -cost - const discards it), which `amis_backward` takes the
+    threshold's gradient from; the other outputs keep their bits."""
     po, pc = _f32c(pose_opt, 'pose_opt'), _f32c(pose_cov, 'pose_cov')
     S, B = int(mc_samples), prob.B
     samples, logw = prob.new(S, B, prob.pose_len), prob.new(S, B)
@@ -482,10 +484,15 @@ def amis_forward(prob, pose_opt, pose_cov, mc_samples, num_iter, eps=1e-5, acg_m
         nz = _f32c(noise, 'noise')
         assert nz.shape == (B, num_iter, S // num_iter, noise_stride(prob.dof)), f'noise shape {tuple(nz.shape)}'
     par, scratch = _amis_struct(prob, S, num_iter, eps, acg_mle_iter, acg_dispersion, seed, offset, offset_dev)
-    _hip.call('epropnp_amis_forward', C.byref(prob.c), C.byref(par), _hip.ptr(po), _hip.ptr(pc), _hip.ptr(nz),
-              _hip.ptr(samples), _hip.ptr(logw), _hip.ptr(props), prob.stream)
+    costs = prob.new(S, B) if with_costs else None
+    if with_costs:
+        _hip.call('epropnp_amis_forward_costs', C.byref(prob.c), C.byref(par), _hip.ptr(po), _hip.ptr(pc), _hip.ptr(nz),
+                  _hip.ptr(samples), _hip.ptr(logw), _hip.ptr(props), _hip.ptr(costs), prob.stream)
+    else:
+        _hip.call('epropnp_amis_forward', C.byref(prob.c), C.byref(par), _hip.ptr(po), _hip.ptr(pc), _hip.ptr(nz),
+                  _hip.ptr(samples), _hip.ptr(logw), _hip.ptr(props), prob.stream)
     del scratch          # stream-ordered reuse by the caching allocator: the launch is enqueued
-    return (samples, logw, props) if with_proposals else (samples, logw)
+    return (samples, logw) + ((props,) if with_proposals else ()) + ((costs,) if with_costs else ())
 
 
 BWD_SPLIT_MAX_SAMPLES = 2600     # the split kernel needs the LDS-resident pose table (csrc/amis_backward_mfma.hip)
@@ -564,9 +571,13 @@ def launch_plan(kind, prob, mc_samples=None, num_iter=None, pose_init=False, nsp
     raise ValueError(f"launch_plan: kind must be 'forward', 'backward' or 'cost', got {kind!r}")
 
 
-def amis_backward(prob, pose_samples, grad_logweights, pose_init=None, grad_cost_init=None, nsplit=None, cstruct=None):
+def amis_backward(prob, pose_samples, grad_logweights, pose_init=None, grad_cost_init=None, nsplit=None, cstruct=None,
+                  sample_costs=None, cost_init=None):
     """-> grad_x3d (B,N,3), grad_x2d (B,N,2), grad_w2d (B,N,2), grad_delta (B,).
-    `cstruct`: a C problem struct to use instead of prob.c (same shapes; the fused path's centred points)."""
+    `cstruct`: a C problem struct to use instead of prob.c (same shapes; the fused path's centred points).
+    `sample_costs` (S,B) from `amis_forward(with_costs=True)` / the one-call forward and `cost_init` (B,), the forward's cost of
+    pose_init: the threshold's gradient is taken from them instead of a per-pair term of the sweep (include/epropnp_hip.h);
+    without them -- or with cost_init missing while pose_init is given -- the per-pair path."""
     B, N = prob.B, prob.N
     cs = prob.c if cstruct is None else cstruct
     S = 0 if pose_samples is None else pose_samples.shape[0]
@@ -577,14 +588,32 @@ def amis_backward(prob, pose_samples, grad_logweights, pose_init=None, grad_cost
         pin, gin = _f32c(pose_init, 'pose_init'), _f32c(grad_cost_init, 'grad_cost_init')
     gx3d, gx2d, gw2d = prob.new(B, N, 3), prob.new(B, N, 2), prob.new(B, N, 2)
     nsplit = backward_split(B, N, S) if nsplit is None else int(nsplit)
+    costs = cin = None
+    if sample_costs is not None and S > 0 and (pin is None or cost_init is not None):
+        costs = _f32c(sample_costs, 'sample_costs')
+        if tuple(costs.shape) != (S, B):
+            raise ValueError(f'sample_costs must be (mc_samples, num_obj) = ({S}, {B}), got {tuple(costs.shape)}')
+        if pin is not None:
+            cin = _f32c(cost_init, 'cost_init')
+            if cin.numel() != B:
+                raise ValueError(f'cost_init must hold num_obj = {B} values, got {tuple(cin.shape)}')
     if nsplit > 1:
         parts = prob.new(B, nsplit)
-        _hip.call('epropnp_amis_backward_split', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin),
-                  _hip.ptr(gin), nsplit, _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(parts), prob.stream)
+        if costs is None:
+            _hip.call('epropnp_amis_backward_split', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin),
+                      _hip.ptr(gin), nsplit, _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(parts), prob.stream)
+        else:
+            _hip.call('epropnp_amis_backward_split_costs', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin),
+                      _hip.ptr(gin), nsplit, _hip.ptr(costs), _hip.ptr(cin), _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d),
+                      _hip.ptr(parts), prob.stream)
         return gx3d, gx2d, gw2d, parts.sum(dim=1)
     gdel = prob.new(B)
-    _hip.call('epropnp_amis_backward', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin), _hip.ptr(gin),
-              _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(gdel), prob.stream)
+    if costs is None:
+        _hip.call('epropnp_amis_backward', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin), _hip.ptr(gin),
+                  _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(gdel), prob.stream)
+    else:
+        _hip.call('epropnp_amis_backward_costs', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin), _hip.ptr(gin),
+                  _hip.ptr(costs), _hip.ptr(cin), _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(gdel), prob.stream)
     return gx3d, gx2d, gw2d, gdel
 
 
@@ -597,11 +626,12 @@ class _MonteCarloCost(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3d, x2d, w2d, delta, prob, pose_opt, pose_cov, pose_init, cost_init_value, cfg):
-        samples, logw = amis_forward(prob, pose_opt, pose_cov, **cfg)
+        samples, logw, costs = amis_forward(prob, pose_opt, pose_cov, with_costs=True, **cfg)
         ctx.set_materialize_grads(False)      # no (S,B,7) zero tensor for the non-differentiable samples output
         ctx.prob, ctx.pose_init = prob, pose_init
         _guard_inputs(ctx, prob)
-        ctx.save_for_backward(samples)
+        # (the samples' costs and the cost of pose_init: the threshold's gradient, amis_backward)
+        ctx.save_for_backward(samples, costs, None if cost_init_value is None else cost_init_value.detach())
         ctx.mark_non_differentiable(samples)
         ctx.delta_shape = delta.shape if isinstance(delta, torch.Tensor) else None
         if cost_init_value is None:
@@ -610,14 +640,15 @@ class _MonteCarloCost(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _g_samples, g_logw, g_cost_init=None):
-        (samples,) = ctx.saved_tensors
+        samples, costs, cost_init = ctx.saved_tensors
         prob = ctx.prob
         if g_logw is None and g_cost_init is None:
             return (None,) * 10
         _check_inputs(ctx)
         if g_logw is None:
             g_logw = torch.full(samples.shape[:2], 0.0, dtype=torch.float32, device=samples.device)
-        gx3d, gx2d, gw2d, gdel = amis_backward(prob, samples, g_logw, ctx.pose_init, g_cost_init)
+        gx3d, gx2d, gw2d, gdel = amis_backward(prob, samples, g_logw, ctx.pose_init, g_cost_init, sample_costs=costs,
+                                               cost_init=cost_init)
         gdelta = None
         if ctx.delta_shape is not None and ctx.needs_input_grad[3]:
             gdelta = gdel.sum() if len(ctx.delta_shape) == 0 else gdel.reshape(ctx.delta_shape)
@@ -660,7 +691,9 @@ class _FusedMonteCarlo(torch.autograd.Function):
         cost = new(B) if with_cost else None
         cost_init = new(B) if pin is not None else None
         pose_opt, samples = (new(B, PL), new(S, B, PL)) if normalize else (None, None)     # caller's frame
+        costs = new(S, B)       # the samples' Huber costs: the backward's threshold gradient (amis_backward)
         p = _hip.ptr
+        _hip.call('epropnp_request_sample_costs', p(costs))      # the forward call below writes them (include/epropnp_hip.h)
         if diag is None:
             _hip.call('epropnp_monte_carlo_forward', C.byref(prob.c), C.byref(par), p(pin), p(nz), p(x3d_c), p(offset), p(pin_n),
                       p(start_pose), p(start_cost), p(pose_opt_n), p(pose_cov), p(cost), p(samples_n), p(logw), p(cost_init),
@@ -682,14 +715,14 @@ class _FusedMonteCarlo(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.prob, ctx.bprob, ctx.keep = prob, bprob, (x3d_c, pin_n if normalize else pin)
         _guard_inputs(ctx, prob)
-        ctx.save_for_backward(samples_n)
+        ctx.save_for_backward(samples_n, costs, cost_init)
         ctx.delta_shape = delta.shape if isinstance(delta, torch.Tensor) else None
         ctx.mark_non_differentiable(*[t for t in (pose_opt_n, samples_n, cost, pose_opt, samples, x3d_c, offset) if t is not None])
         return pose_opt_n, samples_n, logw, cost, cost_init, pose_opt, samples, x3d_c, offset
 
     @staticmethod
     def backward(ctx, _gpn, _gsn, g_logw, _gc, g_cost_init, _gp, _gs, _gx, _go):
-        (samples_n,) = ctx.saved_tensors
+        samples_n, costs, cost_init = ctx.saved_tensors
         prob = ctx.prob
         if g_logw is None and g_cost_init is None:
             return (None,) * 10
@@ -698,7 +731,8 @@ class _FusedMonteCarlo(torch.autograd.Function):
             g_logw = torch.full(samples_n.shape[:2], 0.0, dtype=torch.float32, device=samples_n.device)
         pin = ctx.keep[1]
         gx3d, gx2d, gw2d, gdel = amis_backward(prob, samples_n, g_logw, pin if g_cost_init is not None else None,
-                                               g_cost_init, cstruct=ctx.bprob)
+                                               g_cost_init, cstruct=ctx.bprob, sample_costs=costs,
+                                               cost_init=None if cost_init is None else cost_init.detach())
         gdelta = None
         if ctx.delta_shape is not None and ctx.needs_input_grad[3]:
             gdelta = gdel.sum() if len(ctx.delta_shape) == 0 else gdel.reshape(ctx.delta_shape)

@@ -375,6 +375,50 @@ int epropnp_amis_backward_split(const epropnp_problem* prob, const float* pose_s
                                 int32_t mc_samples, const float* pose_init, const float* grad_cost_init, int32_t num_split,
                                 float* grad_x3d, float* grad_x2d, float* grad_w2d, float* grad_delta_parts, void* stream);
 
+/* ---- The threshold's gradient from the forward's sample costs ------------------------------------------------------------------
+ * grad_delta = sum_pairs a_j max(rho - delta, 0) is the one output of the backward that is a number per object, and its sweep term
+ * sum_pairs a_j min(|r|^2, 1) (residuals r in units of delta) is known before the backward starts: with c1 = min(1, 1 / rho),
+ *     cost_j / delta^2 = sum_n m (rho - m / 2),  m = min(rho, 1)   =   sum_n c1 |r|^2 - 1/2 sum_n min(|r|^2, 1)
+ * (inlier: |r|^2 / 2 on both sides; outlier: rho - 1/2 on both sides), so that
+ *     grad_delta / delta = 2 sum_j a_j cost_j / delta^2 - sum_pairs c1 a_j |r|^2,
+ * where the last sum is what the sweep accumulates for grad_w2d anyway.  cost_j is the Huber cost the AMIS forward computed for
+ * sample j (logw_j = -cost_j - const discards it); the cost of pose_init is the forward's cost_init.  The entries below are the
+ * existing ones with that cost array as one more output (forward) / input (backward):
+ *   sample_costs (S,B), the layout of logweights; cost_init (B,) as epropnp_monte_carlo_forward returns it (= epropnp_evaluate_cost of
+ *   pose_init on the same problem).
+ * Forward: sample_costs == NULL is the existing entry, bit for bit; with it every other output keeps its bits.
+ * Backward: sample_costs == NULL -- or cost_init == NULL while pose_init and grad_cost_init are given, or mc_samples == 0 -- is the
+ * existing entry, bit for bit (the per-pair term).  With the costs grad_x3d, grad_x2d and the sweep's grad_w2d keep their bits;
+ * grad_delta (and its share of grad_w2d under epropnp_problem.delta_stats) agrees with the per-pair form within fp32 rounding of
+ * the two sums, ~ulp * sum_j |a_j| cost_j / delta, not bit for bit.  The costs must be those of pose_samples on THIS problem (same
+ * points, weights, threshold, bounds, z_min); costs of samples that the weight threshold drops are not read and may be anything.
+ * A threshold that the kernels carry as 1e-12 (delta <= 1e-12) makes cost_init -- evaluated at the caller's threshold -- unusable:
+ * the kernel evaluates the cost of pose_init itself for such objects.  huber_eps does not enter: it smooths the solver's Jacobian,
+ * not the Huber value that the sampler and this backward differentiate, so the identity holds for every problem.
+ * The all-VALU kernel (EPROPNP_TUNE=bwd_impl=valu, pose table beyond LDS) ignores the costs; EPROPNP_TUNE=bwd_dcost=0 makes every
+ * launch ignore them.  The launch plan (epropnp_plan_amis_backward) is the same with and without costs. */
+int epropnp_amis_forward_costs(const epropnp_problem* prob, const epropnp_amis_params* amis, const float* pose_opt,
+                               const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
+                               float* proposals, float* sample_costs, void* stream);
+/* epropnp_monte_carlo_forward[_diag] (diag may be NULL) with sample_costs (S,B): the costs of pose_samples_n in the solver frame */
+int epropnp_monte_carlo_forward_costs(const epropnp_problem* prob, const epropnp_mc_params* par, const float* pose_init,
+                                      const float* noise, float* x3d_centered, float* offset, float* pose_init_n,
+                                      float* start_pose, float* start_cost, float* pose_opt_n, float* pose_cov, float* cost,
+                                      float* pose_samples_n, float* logweights, float* cost_init, float* pose_opt,
+                                      float* pose_samples, const epropnp_diag* diag, float* sample_costs, void* stream);
+/* For callers that reach the forward through an interface with a fixed argument list (the package's ctypes nodes): the NEXT call of
+ * epropnp_amis_forward / epropnp_monte_carlo_forward / epropnp_monte_carlo_forward_diag on this host thread also writes its samples'
+ * costs to sample_costs (S,B), as the _costs entries do, and forgets the request whatever it returns.  NULL withdraws a request. */
+int epropnp_request_sample_costs(float* sample_costs);
+int epropnp_amis_backward_costs(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
+                                int32_t mc_samples, const float* pose_init, const float* grad_cost_init,
+                                const float* sample_costs, const float* cost_init, float* grad_x3d, float* grad_x2d,
+                                float* grad_w2d, float* grad_delta, void* stream);
+int epropnp_amis_backward_split_costs(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
+                                      int32_t mc_samples, const float* pose_init, const float* grad_cost_init, int32_t num_split,
+                                      const float* sample_costs, const float* cost_init, float* grad_x3d, float* grad_x2d,
+                                      float* grad_w2d, float* grad_delta_parts, void* stream);
+
 /* AdaptiveHuberPnPCost.set_param (epropnp/cost_fun.py:123-126):
  *   delta[b] = mean(w2d[b]) * sqrt(sum_xy var_N(x2d[b])) * relative_delta      (unbiased variance)
  * x2d (B,N,2), w2d (B,N,2) -> delta (B,), stats (B,4) = [mean_w, x2d_std, mean_x, mean_y] (kept for the backward,
