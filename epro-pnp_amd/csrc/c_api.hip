@@ -218,6 +218,19 @@ int epropnp_posterior_modes(const float* pose_samples, const float* logweights, 
                                      labels, num_modes, mode_index, mode_mass, mode_poses, (hipStream_t)stream);
 }
 
+int epropnp_pose_errors(const float* pose_est, const float* pose_gt, int32_t num_rows_per_obj, int32_t num_obj, int32_t dof,
+                        const float* model_points, const int32_t* model_range, int32_t num_models, const int32_t* model_id,
+                        const float* cam_mats, const uint8_t* symmetric, const uint8_t* half_turn, void* scratch,
+                        size_t scratch_bytes, float* errors, void* stream) {
+  pnp::StageScope prof_("pose_errors", (hipStream_t)stream);
+  return pnp::launch_pose_errors(pose_est, pose_gt, num_rows_per_obj, num_obj, dof, model_points, model_range, num_models, model_id,
+                                 cam_mats, symmetric, half_turn, scratch, scratch_bytes, errors, (hipStream_t)stream);
+}
+
+size_t epropnp_pose_errors_scratch_bytes(int32_t num_rows_per_obj, int32_t num_obj, int32_t max_model_points) {
+  return pnp::pose_errors_scratch_bytes(num_rows_per_obj, num_obj, max_model_points);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);

@@ -279,6 +279,12 @@ int launch_posterior_resample(const float* pose, const float* logw, int S, int B
 int launch_posterior_modes(const float* pose, const float* logw, const float* bandwidth, int S, int B, int dof, float link,
                            int max_modes, float* density, int32_t* parent, int32_t* labels, int32_t* num_modes,
                            int32_t* mode_index, float* mode_mass, float* mode_poses, hipStream_t st);
+// metrics_kernels.hip: pose-error metrics of R x B pose rows against B ground-truth poses (epropnp_pose_errors): the ADD-S
+// nearest-neighbour launch when a symmetric mask is given, then the streaming launch that writes every row
+int launch_pose_errors(const float* pose_est, const float* pose_gt, int R, int B, int dof, const float* points,
+                       const int32_t* range, int C, const int32_t* model_id, const float* cam, const uint8_t* symmetric,
+                       const uint8_t* half_turn, void* scratch, size_t scratch_bytes, float* errors, hipStream_t st);
+size_t pose_errors_scratch_bytes(int R, int B, int max_model_points);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

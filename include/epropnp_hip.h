@@ -17,6 +17,7 @@
 #ifndef EPROPNP_HIP_H
 #define EPROPNP_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -273,6 +274,47 @@ int epropnp_posterior_modes(const float* pose_samples, const float* logweights, 
                             int32_t* num_modes /* (B,) */, int32_t* mode_index /* (M,B) */, float* mode_mass /* (M,B) */,
                             float* mode_poses /* (M,B,P) or NULL */, void* stream);
 
+/* Pose-error metrics of the 6-DoF evaluation, on the device: rotation and translation error, ARP-2D, ADD and ADD-S of
+ * num_rows_per_obj x num_obj pose rows against num_obj ground-truth poses (EPro-PnP-6DoF lib/utils/eval.py:585-736: re, te, arp_2d,
+ * add, adi, calc_all_errs, there a host loop with one scipy cKDTree per symmetric object).  Row (r, b) of pose_est (R,B,P) is scored
+ * against pose_gt[b] over the points of model model_id[b] (model 0 with model_id == NULL): model_points (Mtot,3) holds the models
+ * back to back, model_range[c] = (first point, number of points) of model c.  Quaternions are normalised first; a 4-DoF pose is
+ * (x, y, z, yaw) about the y axis.  Per row, in fp32 (the row's set-up runs in fp64 and is rounded once):
+ *    0  rot_deg     rotation angle of R_est^T R_gt in degrees, 2 atan2(|v|, |w|) of the relative quaternion (what
+ *                   |logm(R_est^T R_gt)|_F / sqrt 2 is, accurate at small angles); 4-DoF: |wrap(yaw_est - yaw_gt)|
+ *    1  trans       |t_est - t_gt|
+ *    2  arp_2d      mean_i |proj(K (R_est p_i + t_est)) - proj(K (R_gt p_i + t_gt))| in pixels, proj a plain division by z (no
+ *                   z_min clamp), K = cam_mats[b]; NaN with cam_mats == NULL
+ *    3  add         mean_i |(R_est p_i + t_est) - (R_gt p_i + t_gt)|, evaluated as |(R_est - R_gt) p_i + (t_est - t_gt)|
+ *    4  adi         ADD-S: mean_i min_j |(R_gt p_i + t_gt) - (R_est p_j + t_est)|, evaluated in the estimate's model frame as
+ *                   min_j |q_i - p_j| with q_i = R_est^T R_gt p_i + R_est^T (t_gt - t_est); only for objects with symmetric[b] != 0,
+ *                   NaN otherwise (and with symmetric == NULL)
+ *    5  add_or_adi  adi where symmetric[b] != 0, else add: what calc_all_errs returns
+ *    6, 7           reserved, 0
+ * half_turn[b] != 0 (the reference's eggbox rule): when the raw rot_deg exceeds 90, rot_deg, trans and arp_2d are taken with
+ * R_est diag(-1, -1, 1) (4-DoF: yaw + pi); add and adi keep the raw estimate.  Identical poses give exact zeros.
+ * ADD-S needs scratch: epropnp_pose_errors_scratch_bytes(R, B, M) bytes serve models of up to M points (one float per row and tile
+ * of EPROPNP_POSE_ERROR_QUERY_TILE points); scratch may be NULL with symmetric == NULL.  What only the device can see gives NaN in
+ * words 0..5 of the row concerned and leaves every other row intact: a model_id outside [0, num_models), a model with first < 0 or
+ * count < 1, a pose component that is not finite, a zero quaternion; a symmetric row whose model has more points than the scratch
+ * serves gets NaN in adi and add_or_adi.  Every word of every row is written.  Two launches on `stream` (one with symmetric ==
+ * NULL), no allocation, no host synchronisation, no floating-point atomics, sums in a fixed order: two launches agree to the last
+ * bit, whatever EPROPNP_TUNE="nn_parts=<workgroups per row>" deals the tiles to.  EPROPNP_EINVAL: a NULL pose_est, pose_gt,
+ * model_points, model_range or errors, a NULL scratch with a symmetric mask, dof not 4 or 6, num_rows_per_obj < 1, num_models < 1,
+ * num_obj < 0, scratch_bytes below epropnp_pose_errors_scratch_bytes(R, B, 1).  num_obj == 0 launches nothing and follows no
+ * pointer.  Capturable into a hipGraph. */
+#define EPROPNP_POSE_ERROR_WORDS 8   /* rot_deg, trans, arp_2d, add, adi, add_or_adi, 0, 0 */
+#define EPROPNP_POSE_ERROR_QUERY_TILE 1024   /* model points per ADD-S query tile: one scratch float per row and tile */
+#define EPROPNP_POSE_ERROR_CAND_TILE 1024    /* model points per LDS tile of ADD-S candidates */
+int epropnp_pose_errors(const float* pose_est /* (R,B,P), R >= 1 */, const float* pose_gt /* (B,P) */,
+                        int32_t num_rows_per_obj /* R */, int32_t num_obj, int32_t dof,
+                        const float* model_points /* (Mtot,3) */, const int32_t* model_range /* (C,2): first, count */,
+                        int32_t num_models, const int32_t* model_id /* (B,) or NULL: model 0 */,
+                        const float* cam_mats /* (B,3,3) or NULL */, const uint8_t* symmetric /* (B,) or NULL */,
+                        const uint8_t* half_turn /* (B,) or NULL */, void* scratch, size_t scratch_bytes,
+                        float* errors /* (R,B,8) */, void* stream);
+size_t epropnp_pose_errors_scratch_bytes(int32_t num_rows_per_obj, int32_t num_obj, int32_t max_model_points);
+
 int epropnp_abi_version(void);
 const char* epropnp_last_error(void);
 
@@ -280,7 +322,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
