@@ -7,8 +7,9 @@
 //   * forward projection  h = (K R | K t)(X,Y,Z,1)^T of 16 poses x 16 points: three MFMAs (A = pose rows from LDS, B = point
 //     tile in registers) -- v_mfma_f32_16x16x4_f32 as in amis_forward_mfma.hip, or (BF16, the default for <= 4 resident
 //     point tiles) ONE v_mfma_f32_16x16x32_bf16 per image row on bf16x3-split operands: fp32-level accuracy at 55 % of the
-//     matrix time (wave_ops.h: ProjOp; the points are split once per chunk, the pose rows on the fly, 21 instructions per
-//     pose tile);
+//     matrix time (wave_ops.h: ProjOp; the points are split once per chunk, the pose rows once per compacted pose while the
+//     table is built -- PRESPLIT below -- or, where the larger table would cost a workgroup per CU, on the fly: 21 instructions
+//     per wave, pose tile and chunk);
 //   * back-projection  g_x3d[n] += sum_j (K R)_j^T g_h[j,n] stays on the VALU (9 FMAs per pair).  It IS expressible as
 //     the same MFMA with the roles swapped (A = the per-pair g_h values, which the forward MFMA leaves in exactly the
 //     lane layout an A operand needs; B = pose rows indexed by output coordinate), and that variant was built and
@@ -52,7 +53,14 @@ constexpr int bwd_min_waves() { return (NPT <= 2) ? PNP_BWD_MINW : PNP_BWD_MINW4
 // pairs (`gsat2`).  cost_j is what the AMIS forward held when it wrote logweights (AmisParams.sample_costs), the cost of pose_init is
 // the forward's cost_init.  grad_delta is then a difference of two sums computed by two kernels -- equal to the per-pair form within
 // rounding, not bit for bit; the per-point gradients do not change.  Callers without costs launch the DCOST = false instantiations.
-template <int DOF, bool BOUNDS, int NPT, bool BF16 = false, bool DCOST = false>
+// PRESPLIT (BF16 only): the bf16-split A operands of the projection come out of the pose table.  The table build, one thread per
+// compacted pose, also stores the split words of the pose's 12 components of (K R | K t) -- wave_ops.h: bf16_split_a_words -- and the
+// sweep reads them back (one 16-byte and one 2-byte LDS read per lane and pose tile, three v_perm) where every wave split three fp32
+// entries per pose tile and chunk (21 instructions).  The same dwords reach the matrix instruction: every output keeps its bits.
+// Layout: qtab[pose][k] = {w0 of the x, y, z row | a3 of the x and y rows as two halves}, ztab[pose][k] = a3 of the z row (16 bits):
+// 18 dwords per pose next to the 15 of the fp32 table, whose K R rows the back-projection still reads (its K t slots are then dead).
+// Storing (a3, a3) as a word would take 24: 89.8 KB per workgroup at C2, where two workgroups per CU leave 80.
+template <int DOF, bool BOUNDS, int NPT, bool BF16 = false, bool DCOST = false, bool PRESPLIT = false>
 __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) void amis_backward_mfma_kernel(Problem p, const float* __restrict__ pose_samples,
                                                                      const float* __restrict__ g_logw, int S,
                                                                      const float* __restrict__ pose_init,
@@ -64,6 +72,7 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
                                                                      const float* __restrict__ cost_init) {
   constexpr int PL = PoseLen<DOF>::value;
   typedef ProjOp<BF16> Proj;      // the projection MFMA: fp32 16x16x4, or the bf16x3 split on 16x16x32 (wave_ops.h)
+  static_assert(!PRESPLIT || BF16, "the pre-split pose rows are operands of the bf16 projection");
   // nsplit > 1 (few objects): an object's point chunks are dealt to nsplit workgroups (v = b * nsplit + part), each with
   // its own copy of the pose table; per-point gradients are disjoint, grad_delta comes out as nsplit partials per object
   const int v = object_of_block(p.B * nsplit);
@@ -74,7 +83,9 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
   PNP_PHASES_BEGIN(6);      // (tuning builds: cycles in [weights | drop threshold | compaction | pose rows | sweep + outputs | tail])
   PNP_DYN_SMEM(float, smem);
   float* ptab = smem;                                   // [P16 / 4][12][4]  (K R | K t) of the compacted poses, four poses per component (below)
-  float* wtab = ptab + 12 * P16;                        // [P16]      weights of the compacted poses
+  u32x4* qtab = reinterpret_cast<u32x4*>(ptab + 12 * P16);                                 // [P16][4]  (PRESPLIT) split words, above
+  unsigned short* ztab = reinterpret_cast<unsigned short*>(qtab + (PRESPLIT ? 4 * P16 : 0));  // [P16][4]  (PRESPLIT)
+  float* wtab = reinterpret_cast<float*>(ztab + (PRESPLIT ? 4 * P16 : 0));                   // [P16]      weights of the compacted poses
   float* wraw = wtab + P16;                             // [P16]      weights by sample index (0 = dropped)
   int* idx = reinterpret_cast<int*>(wraw + P16);        // [P16]      sample index of compacted pose c
   float* red = reinterpret_cast<float*>(idx + P16);     // [80]       reductions, lane counts, active count
@@ -175,6 +186,7 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
   float csum[1] = {0.f};
   for (int c = tid; c < ntile * 16; c += T) {
     float* dst = ptab + (c >> 2) * 48 + (c & 3);
+    float comp[12];      // (K R | K t), component 4 * row + k
     if (c < nact) {
       const int m = idx[c];
       if (DCOST) {
@@ -189,14 +201,29 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
       compose_kr_kt(Kc, R, ps, KR, Kt);
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        dst[(4 * r + 0) * 4] = KR[3 * r]; dst[(4 * r + 1) * 4] = KR[3 * r + 1]; dst[(4 * r + 2) * 4] = KR[3 * r + 2];
-        dst[(4 * r + 3) * 4] = Kt[r];
+        comp[4 * r] = KR[3 * r]; comp[4 * r + 1] = KR[3 * r + 1]; comp[4 * r + 2] = KR[3 * r + 2];
+        comp[4 * r + 3] = Kt[r];
       }
       wtab[c] = wraw[m];
     } else {     // padding of the last tile: a harmless pose (depth 1) with zero weight
 #pragma unroll
-      for (int k = 0; k < 12; ++k) dst[k * 4] = (k == 11) ? 1.f : 0.f;
+      for (int k = 0; k < 12; ++k) comp[k] = (k == 11) ? 1.f : 0.f;
       wtab[c] = 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) dst[k * 4] = comp[k];
+    if constexpr (PRESPLIT) {
+      unsigned zh[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        unsigned w0x, w0y, w0z, w3x, w3y, w3z;
+        bf16_split_a_words(comp[k], w0x, w3x);
+        bf16_split_a_words(comp[4 + k], w0y, w3y);
+        bf16_split_a_words(comp[8 + k], w0z, w3z);
+        qtab[c * 4 + k] = u32x4{w0x, w0y, w0z, bf16_a3_half(w3x) | (bf16_a3_half(w3y) << 16)};
+        zh[k] = bf16_a3_half(w3z);
+      }
+      *reinterpret_cast<u32x2*>(ztab + c * 4) = u32x2{zh[0] | (zh[1] << 16), zh[2] | (zh[3] << 16)};
     }
   }
   __syncthreads();
@@ -243,8 +270,17 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
     // per pair less -- chosen per tile by a bound on |X|: no gain at C2 for the reason above, and 10-20 us more per launch at the
     // few-object shapes for the bound's extra pass and barriers; removed.)
     for (int t = 0; t < ntile; ++t) {
-      const float* grp = ptab + (t * 4 + (col >> 2)) * 48 + (col & 3);
-      const typename Proj::T ax = Proj::a(grp[kk * 4]), ay = Proj::a(grp[(4 + kk) * 4]), az = Proj::a(grp[(8 + kk) * 4]);
+      typename Proj::T ax, ay, az;
+      if constexpr (PRESPLIT) {      // A operands rebuilt from the stored words of pose (tile t, row col), k-slice kk
+        const u32x4 q = qtab[(t * 16 + col) * 4 + kk];
+        const unsigned z = ztab[(t * 16 + col) * 4 + kk];
+        ax = bf16_a_from_words(q[0], bf16_dup_lo(q[3]));
+        ay = bf16_a_from_words(q[1], bf16_dup_hi(q[3]));
+        az = bf16_a_from_words(q[2], bf16_dup_lo(z));
+      } else {
+        const float* grp = ptab + (t * 4 + (col >> 2)) * 48 + (col & 3);
+        ax = Proj::a(grp[kk * 4]); ay = Proj::a(grp[(4 + kk) * 4]); az = Proj::a(grp[(8 + kk) * 4]);
+      }
       const float4 aw4 = *reinterpret_cast<const float4*>(wtab + t * 16 + g4);
       // this lane's 4 poses: rows of K R (the back-projection), one float4 = one component of the four poses
       const float4* rows = reinterpret_cast<const float4*>(ptab + (t * 4 + kk) * 48);
@@ -424,7 +460,7 @@ static int dispatch_bwd_npt(int npt, F&& f) {
 struct BwdPlan {
   int waves, npt, P16, gw_rows;
   size_t smem;
-  bool bf16;
+  bool bf16, presplit;
 };
 
 // Which instantiation launch_amis_backward_mfma launches, and with what shape: a pure host function of the sizes, the tuning
@@ -469,7 +505,18 @@ static int plan_amis_backward(const epropnp_problem* prob, int mc_samples, bool 
   // its points are split over workgroups -- the per-point gradients of the split and the unsplit launch are the same bits.)
   bool bf16 = true;
   if (const char* e = getenv("EPROPNP_BWD_PROJ")) bf16 = (e[0] == 'f') ? false : (e[0] == 'b' ? true : bf16);
-  out->waves = waves; out->npt = npt; out->P16 = P16; out->gw_rows = gw_rows; out->smem = smem; out->bf16 = bf16;
+  // Pose rows split to bf16 once, by the table build (kernel comment: PRESPLIT): 18 dwords per pose more.  Taken only where the larger
+  // table does not lower the workgroups per CU of the shape -- two for four resident tiles, three for one and two (the register budgets
+  // above) -- with the parked grad_w2d rows kept where they are parked today: C2 (S = 512, four tiles) 76.8 KB per workgroup, the Det
+  // shape (S = 128, two tiles) fits three; two tiles at S = 512 keep the split on the fly.  EPROPNP_TUNE=bwd_presplit=0 forces that path.
+  bool presplit = false;
+  if (bf16) {
+    const size_t pre = smem + sizeof(float) * 18 * (size_t)P16;
+    presplit = (size_t)(npt == 4 ? 2 : 3) * pre <= 160 * 1024;
+    { int ov[1]; if (tune_ints("bwd_presplit", ov, 1) && ov[0] == 0) presplit = false; }
+    if (presplit) smem = pre;
+  }
+  out->waves = waves; out->npt = npt; out->P16 = P16; out->gw_rows = gw_rows; out->smem = smem; out->bf16 = bf16; out->presplit = presplit;
   return 0;
 }
 
@@ -511,6 +558,9 @@ int launch_amis_backward_mfma(const epropnp_problem* prob, const float* pose_sam
     return dispatch_bwd_npt(npt, [&](auto NPT) -> int {
       constexpr int kDof = decltype(DOF)::value, kNpt = decltype(NPT)::value;
       constexpr bool kBnd = decltype(BND)::value;
+      if (plan.presplit)
+        return dcost ? launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true, true, true>)
+                     : launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true, false, true>);
       if (dcost)
         return bf16 ? launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true, true>)
                     : launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, false, true>);

@@ -140,6 +140,7 @@ __device__ __forceinline__ bool uniform_is_zero(float a) { return __builtin_amdg
 // VALU dependence from the recogniser (the asm "redefines" the register), which is what made the round-3 attempts at this
 // projection wrong and run-to-run different (profiles/r04_bwd_bf16_projection.txt).
 typedef unsigned u32x4 __attribute__((vector_size(16)));
+typedef unsigned u32x2 __attribute__((vector_size(8)));
 __device__ __forceinline__ floatx4 mfma_16x16x32_bf16(u32x4 a, u32x4 b, floatx4 c) {
   typedef __bf16 bf16x8_ __attribute__((vector_size(16)));
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_, a), __builtin_bit_cast(bf16x8_, b), c, 0, 0, 0);
@@ -160,11 +161,25 @@ __device__ __forceinline__ void bf16_split3(float x, unsigned& p1, unsigned& p2,
   const float r2 = r1 - f2;                      // exact, <= 8 significant bits left: a bf16 value
   __builtin_memcpy(&p3, &r2, 4);
 }
-__device__ __forceinline__ u32x4 bf16_split_a(float a) {      // (a1,a2) (a1,a2) (a1,a2) (a3,a3)
+// The A operand (a1,a2) (a1,a2) (a1,a2) (a3,a3) holds two distinct words.  A table that is written once and read per pose tile
+// stores those (store form) and rebuilds the tuple behind the read (load form): the split -- 7 instructions per component -- then
+// runs once per table entry instead of once per wave and sweep.  w3 repeats one bf16 in both halves, so a table short of LDS keeps
+// 16 bits of it (bf16_a3_half) and re-forms the word with one v_perm (bf16_dup_lo / bf16_dup_hi: two halves travel in one dword).
+// Same dwords as bf16_split_a for every bit pattern, which is written on top of the pair below.
+__device__ __forceinline__ void bf16_split_a_words(float a, unsigned& w0, unsigned& w3) {
   unsigned a1, a2, a3;
   bf16_split3(a, a1, a2, a3);
-  const unsigned w0 = bf16_pack_hi(a1, a2);
-  return u32x4{w0, w0, w0, bf16_pack_hi(a3, a3)};
+  w0 = bf16_pack_hi(a1, a2);
+  w3 = bf16_pack_hi(a3, a3);
+}
+__device__ __forceinline__ u32x4 bf16_a_from_words(unsigned w0, unsigned w3) { return u32x4{w0, w0, w0, w3}; }
+__device__ __forceinline__ unsigned bf16_a3_half(unsigned w3) { return w3 >> 16; }
+__device__ __forceinline__ unsigned bf16_dup_lo(unsigned h) { return __builtin_amdgcn_perm(h, h, 0x01000100u); }      // {lo16, lo16}
+__device__ __forceinline__ unsigned bf16_dup_hi(unsigned h) { return __builtin_amdgcn_perm(h, h, 0x03020302u); }      // {hi16, hi16}
+__device__ __forceinline__ u32x4 bf16_split_a(float a) {      // (a1,a2) (a1,a2) (a1,a2) (a3,a3)
+  unsigned w0, w3;
+  bf16_split_a_words(a, w0, w3);
+  return bf16_a_from_words(w0, w3);
 }
 __device__ __forceinline__ u32x4 bf16_split_b(float b) {      // (b1,b1) (b2,b2) (b3,b3) (b1,b2)
   unsigned b1, b2, b3;

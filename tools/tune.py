@@ -71,6 +71,8 @@ def worker(B, N, S, K, L, reps=8):
 
 VARIANTS = [
     ('default', {}),
+    # the backward's pose rows split to bf16 on the fly by every wave of the sweep, instead of once while the pose table is built
+    ('bwd_split_on_the_fly', {'EPROPNP_TUNE': 'bwd_presplit=0'}),
 ]
 # TUNE_VARIANTS="name:KEY=VAL+KEY=VAL|name2:KEY=VAL" adds variants without editing this file.  An UPPER-CASE key is an environment
 # variable of its own (the user-facing knobs: EPROPNP_BWD_DROP, EPROPNP_FWD_PROJ ...), a lower-case key goes into the one tuning
