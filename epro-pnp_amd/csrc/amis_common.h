@@ -157,12 +157,17 @@ PNP_FIT_FN void fit_translation(fit_t (&C)[3][3], const float* fallback_diag, fl
 // totals come back as broadcast reads: ~35 VALU instructions for 21 values.  Fixed order: bit-reproducible.
 constexpr int kRefitMaxVals = 21;
 constexpr int kRefitRedFloats = kRefitMaxVals * kSumTRow + 24;     // rows of 64 + 4 floats, then the totals
+// The same reductions in a scratch of 11 rows: the 21 moments go through it as 11 + 10 (amis_refit<DOF, true>).  A row's sum does not
+// depend on which rows share its pass -- the same four lane quarters add the same 16 columns each in the same order --, so the totals
+// keep their bits.
+constexpr int kRefitHalfVals = 11;
+constexpr int kRefitHalfFloats = kRefitHalfVals * kSumTRow + 24;
 
 // (lane: the caller's lane index -- passed in so that a kernel can hand over an opaque copy, amis_forward_mfma.hip)
-template <int NV>
+template <int NV, int ROWS = kRefitMaxVals>
 PNP_FN void wave_sum_t(float (&v)[NV], float* lds, int lane) {
-  static_assert(NV <= kRefitMaxVals, "scratch rows");
-  float* tot = lds + kRefitMaxVals * kSumTRow;
+  static_assert(NV <= ROWS, "scratch rows");
+  float* tot = lds + ROWS * kSumTRow;
 #pragma unroll
   for (int i = 0; i < NV; ++i) lds[i * kSumTRow + lane] = v[i];
   wave_lds_fence();
@@ -185,10 +190,10 @@ PNP_FN void wave_sum_t(float (&v)[NV], float* lds, int lane) {
 }
 
 // the refit's cross-lane sums: transposed through `scratch`, or (no scratch: the all-VALU forward kernel) wave_sum chains
-template <int NV>
+template <int NV, int ROWS = kRefitMaxVals>
 PNP_FN void refit_sum(float (&v)[NV], float* scratch, int lane) {
   if (scratch != nullptr) {
-    wave_sum_t<NV>(v, scratch, lane);
+    wave_sum_t<NV, ROWS>(v, scratch, lane);
   } else {
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
@@ -683,8 +688,12 @@ PNP_FN void amis_weights(const AmisCtx& cx, const AmisParams& a, int it, int WP)
 // and a sum of squares instead of a cancelling quadratic form), the weights
 // are divided by hardware reciprocals, and the translation factor is fitted by lane 1 inside the instruction stream of lane
 // 0's rotation fit (fit_factor_pair).
-template <int DOF>
+// HALF: cx.rred holds kRefitHalfFloats only (the forward with the per-tile weights in LDS lends it the partial-cost rows, which
+// are dead here); 6-DoF.
+template <int DOF, bool HALF = false>
 PNP_FN void amis_refit(const AmisCtx& cx, const AmisParams& a, int it) {
+  static_assert(!HALF || DOF == 6, "the half-size scratch serves the 6-DoF refit");
+  constexpr int ROWS = HALF ? kRefitHalfVals : kRefitMaxVals;
   float* smp = cx.smp; float* lgw = cx.lgw; float* prop = cx.prop; float* red = cx.red;
   const int S = cx.S, s = cx.s;
   const float* rec = prop + it * kPropStride;
@@ -730,7 +739,23 @@ PNP_FN void amis_refit(const AmisCtx& cx, const AmisParams& a, int it) {
       mom[16] += iw * q3 * q0; mom[17] += iw * q3 * q1; mom[18] += iw * q3 * q2; mom[19] += iw * q3 * q3;
       mom[20] += iw;
     }
-    if (!PNP_ABLATED(a, 16)) refit_sum<21>(mom, cx.rred, tid);
+    if (!PNP_ABLATED(a, 16)) {
+      if constexpr (HALF) {
+        float lo[11], hi[10];
+#pragma unroll
+        for (int i = 0; i < 11; ++i) lo[i] = mom[i];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) hi[i] = mom[11 + i];
+        refit_sum<11, ROWS>(lo, cx.rred, tid);
+        refit_sum<10, ROWS>(hi, cx.rred, tid);
+#pragma unroll
+        for (int i = 0; i < 11; ++i) mom[i] = lo[i];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) mom[11 + i] = hi[i];
+      } else {
+        refit_sum<21>(mom, cx.rred, tid);
+      }
+    }
     const float invZ = 1.0f / mom[0];
     const float dl0 = mom[1] * invZ, dl1 = mom[2] * invZ, dl2 = mom[3] * invZ;
     const float mu0 = p0 + dl0, mu1 = p1 + dl1, mu2 = p2 + dl2;
@@ -788,7 +813,7 @@ PNP_FN void amis_refit(const AmisCtx& cx, const AmisParams& a, int it) {
         acc[3] += iw * q2 * q0; acc[4] += iw * q2 * q1; acc[5] += iw * q2 * q2;
         acc[6] += iw * q3 * q0; acc[7] += iw * q3 * q1; acc[8] += iw * q3 * q2; acc[9] += iw * q3 * q3;
       }
-      refit_sum<11>(acc, cx.rred, tid);
+      refit_sum<11, ROWS>(acc, cx.rred, tid);
     }
     PNP_REFIT_PHASE(1);
     if (tid < 2) {      // lane 0: rotation factor, lane 1: translation factor (the same instructions)

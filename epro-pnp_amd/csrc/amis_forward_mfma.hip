@@ -92,10 +92,15 @@ struct MfmaShape {
 // row cannot double as the weighted operand, so the weights are NOT folded into the B operands here (two more multiplies per
 // point-pose) and the 6-DoF kernel is compiled for three waves per SIMD instead of four (152 VGPRs): still -9 % at C2
 // (profiles/r04_fwd_bf16_projection.txt).
-template <int DOF, bool BOUNDS, int NPT, bool SPILL = false, bool SPLIT = false, bool BF16 = false, bool CHUNKED = false>
+// WLDS (register mode, BF16, 6-DoF, one workgroup per object, not chunked): the per-tile weights (w_u, w_v, -u w_u, -v w_v) live in LDS
+// -- [waves x NPT tiles][16 columns] of float4, written once by load_tiles -- instead of 4 VGPRs per resident tile, and the sweep reads
+// one float4 per resident tile and pose tile, tile i + 1's where the pipeline issues tile i + 1's projections.  That brings the
+// eight-tile kernel from 168 to under 128 VGPRs: four waves per SIMD, four workgroups per CU where the LDS allows (plan_amis_forward).
+// The 8 KB come out of the refit's reduction scratch, which moves onto the partial-cost rows (dead during the refit) at half its size.
+template <int DOF, bool BOUNDS, int NPT, bool SPILL = false, bool SPLIT = false, bool BF16 = false, bool CHUNKED = false, bool WLDS = false>
 // (SPLIT grids are sized for one workgroup per CU: two waves per SIMD -- 256 VGPRs -- leave room for a second such launch and
 // for the part-recomputation path's second copy of the sweep without spilling)
-__global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PNP_FWD_BF16_MINW : PNP_FWD_MINW) : 2) : (NPT <= 2 ? 3 : 2))) void amis_forward_mfma_kernel(Problem p, AmisParams a_in, MfmaShape sh,
+__global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? (WLDS ? PNP_FWD_WLDS_MINW : PNP_FWD_BF16_MINW) : PNP_FWD_MINW) : 2) : (NPT <= 2 ? 3 : 2))) void amis_forward_mfma_kernel(Problem p, AmisParams a_in, MfmaShape sh,
                                                                   const float* __restrict__ pose_opt,
                                                                   const float* __restrict__ pose_cov,
                                                                   const float* __restrict__ noise,
@@ -106,6 +111,7 @@ __global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PN
                                                                   float* __restrict__ xch) {
   static_assert(!SPILL || NPT == 0, "the spill variant streams the points");
   static_assert(!SPLIT || NPT > 0, "the split over workgroups is a register-mode variant");
+  static_assert(!WLDS || (BF16 && DOF == 6 && NPT > 0 && !SPLIT && !CHUNKED && !SPILL), "weights in LDS: the one-workgroup bf16 6-DoF kernel");
   constexpr int PL = PoseLen<DOF>::value;
   // nsplit = G > 1 (few objects, register mode): G workgroups share one object.  Each runs the whole sampler -- draws, weights
   // and proposal fits are deterministic, so the G copies stay identical -- but sweeps only every G-th group of point tiles;
@@ -154,11 +160,15 @@ __global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PN
   // follows them is read as float4 (cpart rows, the refit's rred): the block is rounded up, here and in the launcher's lds_bytes)
   float* cpart = SPILL ? pW + 4 * NC : smp + (((PL + 3) * S + 3) & ~3);      // [WPs][s16]
   float* gath = cpart + W * s16;             // [G][s16] (SPLIT) the parts' partial costs of the current iteration
-  float* prop = cpart + cpart_rows * s16 + (SPLIT ? 4 : 0);    // [K][kPropStride]  (SPLIT: + the missing-parts word)
+  // WLDS: the refit's scratch (half size, amis_refit<DOF, true>) IS the cpart block, which is at least that large.  cpart is written by
+  // the sweep and read by amis_weights; the barrier behind amis_weights hands it to wave 0's refit, the barrier that ends the refit
+  // (and the one behind the next draw) hands it back to the sweep.
+  float* prop = cpart + (WLDS ? max(cpart_rows * s16, kRefitHalfFloats) : cpart_rows * s16) + (SPLIT ? 4 : 0);    // [K][kPropStride]  (SPLIT: + the missing-parts word)
   float* red = prop + K * kPropStride;   // [256]
-  float* rred = red + 256;               // [kRefitRedFloats] the refit's transposed reductions (amis_common.h: wave_sum_t)
-  float* nzb = (s <= T) ? ptab : rred + kRefitRedFloats;   // [s][8] base noise drawn ahead; shares the pose table's LDS when
-                                              // one sample per lane suffices (amis_draw separates the two uses)
+  float* wl = red + 256;                 // (WLDS) [W x NPT][16] float4: the resident tiles' weights                  (16-B aligned)
+  float* rred = WLDS ? cpart : red + 256;      // [kRefitRedFloats] the refit's transposed reductions (amis_common.h: wave_sum_t)
+  float* nzb = (s <= T) ? ptab : (WLDS ? wl + W * NPT * 64 : rred + kRefitRedFloats);   // [s][8] base noise drawn ahead; shares the pose
+                                              // table's LDS when one sample per lane suffices (amis_draw separates the two uses)
 
   float Kc[9], delta;
   Bounds bd;
@@ -192,17 +202,22 @@ __global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PN
   };
   // register mode: this wave's point tiles q = wv + W * i of part `pt`, lane = (point column, k)
   typename Proj::T rB[kRegs ? NPT : 1];
-  float4 rW[kRegs ? NPT : 1];
+  float4 rW[kRegs ? NPT : 1];      // (WLDS: unused, the weights go to wl)
   auto load_tiles = [&](int pt) {
 #pragma unroll
     for (int i = 0; i < (kRegs ? NPT : 1); ++i) {
       const Point q = load_point(p, b, ((pt * W + wv) + GT * W * i) * 16 + (lane & 15));      // zero weight beyond N
       const int k4 = lane >> 4;
+      const int wslot = (wv * NPT + i) * 16 + (lane & 15);      // (WLDS) this tile's row of wl, this lane's column
       const float bval = (k4 == 0) ? q.X : (k4 == 1) ? q.Y : (k4 == 2) ? q.Z : 1.0f;
       rB[i] = Proj::b(bval);
       // without a projection clamp the weights are folded into the B operands of the x and y rows (same 5 VGPRs)
       const float wu = q.wu * inv_delta, wv = q.wv * inv_delta;
-      rW[i] = kFold ? make_float4(bval * wu, bval * wv, -q.u * wu, -q.v * wv) : make_float4(wu, wv, -q.u * wu, -q.v * wv);
+      if constexpr (WLDS) {
+        if (k4 == 0) reinterpret_cast<float4*>(wl)[wslot] = make_float4(wu, wv, -q.u * wu, -q.v * wv);
+      } else {
+        rW[i] = kFold ? make_float4(bval * wu, bval * wv, -q.u * wu, -q.v * wv) : make_float4(wu, wv, -q.u * wu, -q.v * wv);
+      }
     }
   };
   if (kRegs) {
@@ -229,12 +244,22 @@ __global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PN
       constexpr int NT = kRegs ? NPT : 1;
       constexpr bool kPipe = (PNP_FWD_PIPE != 0) && !kFold && NT >= 4;      // (tuning.h: software pipeline over the resident tiles)
       floatx4 hxn = zero, hyn = zero, hzn = zero;
+      // WLDS: this lane's column of the wave's weight rows, tile i at wl4[16 i]; tile i + 1's float4 is fetched next to its projections
+      // and waited for only where tile i + 1 consumes it (LDS reads return in order: the compiler's lgkmcnt is counted)
+      const float4* wl4 = reinterpret_cast<const float4*>(wl) + wv * NPT * 16 + col;
+      float4 wn = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (WLDS) wn = wl4[0];
       if (kPipe) {
         hxn = Proj::mma(ax, rB[0], zero); hyn = Proj::mma(ay, rB[0], zero); hzn = Proj::mma(az, rB[0], zero);
       }
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
         floatx4 hx, hy, hz;
+        float4 w4 = rW[i];
+        if constexpr (WLDS) {
+          w4 = wn;
+          if (!kPipe && i + 1 < NT) wn = wl4[16 * (i + 1)];
+        }
         if constexpr (kFold) {
           hx = mfma_16x16x4(ax, rW[i].x, zero);
           hy = mfma_16x16x4(ay, rW[i].y, zero);
@@ -242,6 +267,7 @@ __global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PN
         } else if constexpr (kPipe) {
           hx = hxn; hy = hyn; hz = hzn;
           if (i + 1 < NT) {
+            if constexpr (WLDS) wn = wl4[16 * (i + 1)];
             hxn = Proj::mma(ax, rB[i + 1], zero);
             hyn = Proj::mma(ay, rB[i + 1], zero);
             hzn = Proj::mma(az, rB[i + 1], zero);
@@ -252,7 +278,7 @@ __global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PN
           hy = Proj::mma(ay, rB[i], zero);
           hz = Proj::mma(az, rB[i], zero);
         }
-        huber_cost_4<BOUNDS, kFold>(hx, hy, hz, rW[i], zmin_v, one_v, bd, acc2);
+        huber_cost_4<BOUNDS, kFold>(hx, hy, hz, w4, zmin_v, one_v, bd, acc2);
       }
       // the four poses' sums over this row's 16 points: lane col < 4 ends up with pose g4 + col (wave_ops.h: row_sum16_of4)
       const float acc[4] = {acc2[0][0], acc2[0][1], acc2[1][0], acc2[1][1]};
@@ -390,7 +416,7 @@ __global__ __launch_bounds__(512, SPLIT ? 2 : (DOF == 6 ? (NPT <= 8 ? (BF16 ? PN
     __syncthreads();
     PNP_PHASE(3);
     if (it == K - 1) break;
-    amis_refit<DOF>(cxw, a, it);
+    amis_refit<DOF, WLDS>(cxw, a, it);
     PNP_PHASE(4);
   }
 
@@ -458,7 +484,10 @@ struct FwdPlan {
   int waves, npt, G;      // npt == 0: the points stream through LDS
   size_t smem;
   bool bf16, spilled, truncated, chunked;      // truncated: a pose tile of the spill variant holds less than an iteration's samples
+  bool wlds;                                   // the per-tile weights in LDS (kernel comment: WLDS)
 };
+
+constexpr size_t kLdsPerCu = 160 * 1024, kLdsGranule = 1280;      // gfx950: LDS is handed out in blocks of 320 dwords
 
 // Which instantiation launch_amis_forward_mfma launches for a problem, and with what shape: a pure host function of the sizes,
 // the tuning variables and the CU count (launches nothing, reads no device memory).  The launcher below calls it, and so does
@@ -523,10 +552,18 @@ static int plan_amis_forward(const epropnp_problem* prob, int S, int K, unsigned
   }
   if (sh.chunks < 1) sh.chunks = 1;
   sh.ahead = 1;
-  auto lds_bytes = [&](bool spilled) {
+  // Floats of a workgroup, in the kernel's order: pose table 12 s16 | point chunk 8 chunk | sampler state (PL + 3) S rounded up to 4 |
+  // partial-cost rows | proposals 40 K | red 256 | refit scratch | noise drawn ahead 8 s unless it shares the pose table.
+  // At C2 (s16 = 128, S = 512, K = 4, 4 waves): 1536 + 0 + 5120 + 512 + 160 + 256 + 1452 = 9036 floats = 36,144 B.
+  // wlds: the refit scratch, at half size (kRefitHalfFloats = 772), IS the partial-cost block, which grows to hold it, and the weights
+  // take waves x npt x 64 floats in the scratch's old place -- C2: 1536 + 5120 + 772 + 160 + 256 + 2048 = 9892 floats = 39,568 B, 31 LDS
+  // granules, four workgroups per CU (40,960 B each).
+  auto lds_bytes = [&](bool spilled, bool wlds = false) {
+    size_t cp = (size_t)(npt ? (G > 1 ? waves + G : waves) : 1) * sh.s16;
+    if (wlds && cp < (size_t)kRefitHalfFloats) cp = kRefitHalfFloats;
     return sizeof(float) * (12 * (size_t)sh.s16 + 8 * (size_t)sh.chunk + (spilled ? 0 : (((size_t)(PL + 3) * S + 3) & ~(size_t)3)) +
-                            (size_t)(npt ? (G > 1 ? waves + G : waves) : 1) * sh.s16 + (G > 1 ? 4 : 0) + (size_t)K * kPropStride + 256 +
-                            kRefitRedFloats +
+                            cp + (G > 1 ? 4 : 0) + (size_t)K * kPropStride + 256 +
+                            (wlds ? (size_t)64 * waves * npt : (size_t)kRefitRedFloats) +
                             ((s <= 64 * waves || !sh.ahead) ? 0 : 8 * (size_t)s));      // (s <= lanes: the noise shares the pose table)
   };
   size_t smem = lds_bytes(false);
@@ -562,6 +599,24 @@ static int plan_amis_forward(const epropnp_problem* prob, int S, int K, unsigned
   out->bf16 = bf16; out->spilled = spilled; out->truncated = sh.s16 < s16_full;
   // (the knob: the chunked instantiation with one chunk)
   out->chunked = !spilled && G == 1 && npt == 8 && (sh.chunks > 1 || (bf16 && tune_flag("fwd_chunked")));
+  // Weights in LDS (kernel comment: WLDS) where that buys the fourth workgroup per CU: the instantiated shape (6-DoF, bf16, 4 waves x 8
+  // tiles, one workgroup per object, not chunked), four of the new size -- in LDS granules -- in a CU's 160 KiB, and a grid of more than
+  // the three workgroups per CU that today's 168 VGPRs allow.  EPROPNP_TUNE=fwd_wlds=0: never; =1: wherever instantiated and it fits LDS.
+  out->wlds = false;
+  if (prob->dof == 6 && bf16 && !spilled && !out->chunked && G == 1 && waves == 4 && npt == 8) {
+    const size_t smem_w = lds_bytes(false, true);
+    const size_t granules = (smem_w + kLdsGranule - 1) / kLdsGranule * kLdsGranule;
+    bool take = 4 * granules <= kLdsPerCu && (long)padded_object_grid(B) > 3L * device_cu_count();
+    { int ov[1]; if (tune_ints("fwd_wlds", ov, 1)) take = ov[0] != 0 && smem_w <= kLdsPerCu; }
+    if (take) { out->wlds = true; out->smem = smem_w; }
+    // (a tuning build that compiles the instantiation for fewer waves per SIMD also asks for the LDS that holds a CU at that many
+    // workgroups: the kernel needs 106 VGPRs whatever its bound, so the bound alone would not separate the cost of the LDS reads from
+    // the gain of the fourth workgroup)
+    if (take && PNP_FWD_WLDS_MINW < 4) {
+      const size_t hold = kLdsPerCu / PNP_FWD_WLDS_MINW / kLdsGranule * kLdsGranule;
+      if (out->smem < hold) out->smem = hold;
+    }
+  }
   return EPROPNP_OK;
 }
 
@@ -670,6 +725,10 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
         if constexpr (decltype(NPT)::value == 8) {
           if (plan.chunked)
             return run(amis_forward_mfma_kernel<decltype(DOF)::value, decltype(BND)::value, 8, false, false, true, true>);
+          if constexpr (decltype(DOF)::value == 6) {
+            if (plan.wlds)
+              return run(amis_forward_mfma_kernel<6, decltype(BND)::value, 8, false, false, true, false, true>);
+          }
         }
         if constexpr (decltype(NPT)::value >= 1) {
           if (bf16) return run(amis_forward_mfma_kernel<decltype(DOF)::value, decltype(BND)::value, decltype(NPT)::value, false, false, true>);

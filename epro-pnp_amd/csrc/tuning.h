@@ -17,6 +17,9 @@
 #ifndef PNP_FWD_BF16_MINW  // waves per SIMD the split-projection 6-DoF forward with <= 8 resident tiles is compiled for
 #define PNP_FWD_BF16_MINW 3
 #endif
+#ifndef PNP_FWD_WLDS_MINW  // ... with the per-tile weights in LDS instead of registers (WLDS: 107 VGPRs, four workgroups per CU)
+#define PNP_FWD_WLDS_MINW 4
+#endif
 #ifndef PNP_FWD_PIPE       // 1: the forward's sweep issues tile i + 1's projections in front of tile i's Huber sweep (round 6: -4.7 % at C2)
 #define PNP_FWD_PIPE 1
 #endif

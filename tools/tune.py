@@ -73,6 +73,8 @@ VARIANTS = [
     ('default', {}),
     # the backward's pose rows split to bf16 on the fly by every wave of the sweep, instead of once while the pose table is built
     ('bwd_split_on_the_fly', {'EPROPNP_TUNE': 'bwd_presplit=0'}),
+    # the forward's per-tile weights in registers (168 VGPRs, three workgroups per CU at C2) instead of LDS (106, four)
+    ('fwd_weights_in_registers', {'EPROPNP_TUNE': 'fwd_wlds=0'}),
 ]
 # TUNE_VARIANTS="name:KEY=VAL+KEY=VAL|name2:KEY=VAL" adds variants without editing this file.  An UPPER-CASE key is an environment
 # variable of its own (the user-facing knobs: EPROPNP_BWD_DROP, EPROPNP_FWD_PROJ ...), a lower-case key goes into the one tuning
