@@ -231,6 +231,21 @@ size_t epropnp_pose_errors_scratch_bytes(int32_t num_rows_per_obj, int32_t num_o
   return pnp::pose_errors_scratch_bytes(num_rows_per_obj, num_obj, max_model_points);
 }
 
+int epropnp_bev_overlap(const float* boxes_a, int32_t num_a, const float* boxes_b, int32_t num_b, int32_t want_iou, int32_t aligned,
+                        float* out, void* stream) {
+  pnp::StageScope prof_("bev_overlap", (hipStream_t)stream);
+  return pnp::launch_bev_overlap(boxes_a, num_a, boxes_b, num_b, want_iou, aligned, out, (hipStream_t)stream);
+}
+
+size_t epropnp_bev_nms_scratch_bytes(int32_t num_boxes) { return pnp::bev_nms_scratch_bytes(num_boxes); }
+
+int epropnp_bev_nms(const float* boxes, const int32_t* order, const int32_t* group, int32_t num_boxes, float iou_thr, void* scratch,
+                    size_t scratch_bytes, int32_t* keep_index, uint8_t* keep_mask, int32_t* num_keep, void* stream) {
+  pnp::StageScope prof_("bev_nms", (hipStream_t)stream);
+  return pnp::launch_bev_nms(boxes, order, group, num_boxes, iou_thr, scratch, scratch_bytes, keep_index, keep_mask, num_keep,
+                             (hipStream_t)stream);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);

@@ -285,6 +285,13 @@ int launch_pose_errors(const float* pose_est, const float* pose_gt, int R, int B
                        const int32_t* range, int C, const int32_t* model_id, const float* cam, const uint8_t* symmetric,
                        const uint8_t* half_turn, void* scratch, size_t scratch_bytes, float* errors, hipStream_t st);
 size_t pose_errors_scratch_bytes(int R, int B, int max_model_points);
+// boxes_kernels.hip: rotated BEV boxes (epropnp_bev_overlap, epropnp_bev_nms): pairwise / aligned overlap or IoU in one launch; the
+// grouped greedy suppression in two (the 64 x 64 mask tiles of the visiting order, then the one-workgroup reduce)
+int launch_bev_overlap(const float* boxes_a, int M, const float* boxes_b, int N, int want_iou, int aligned, float* out,
+                       hipStream_t st);
+int launch_bev_nms(const float* boxes, const int32_t* order, const int32_t* group, int N, float thr, void* scratch,
+                   size_t scratch_bytes, int32_t* keep_index, uint8_t* keep_mask, int32_t* num_keep, hipStream_t st);
+size_t bev_nms_scratch_bytes(int N);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

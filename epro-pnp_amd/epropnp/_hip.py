@@ -98,6 +98,10 @@ def _declare(lib):
     lib.epropnp_pose_errors.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.epropnp_pose_errors_scratch_bytes.argtypes = [i32, i32, i32]
     lib.epropnp_pose_errors_scratch_bytes.restype = C.c_size_t
+    lib.epropnp_bev_overlap.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
+    lib.epropnp_bev_nms.argtypes = [vp, vp, vp, i32, C.c_float, vp, C.c_size_t, vp, vp, vp, vp]
+    lib.epropnp_bev_nms_scratch_bytes.argtypes = [i32]
+    lib.epropnp_bev_nms_scratch_bytes.restype = C.c_size_t
     lib.epropnp_evaluate_cost.argtypes = [C.POINTER(Problem), vp, i32, vp, vp]
     lib.epropnp_normal_equations.argtypes = [C.POINTER(Problem), vp, i32, vp, vp, vp, vp]
     lib.epropnp_cost_pose_cam_grad.argtypes = [C.POINTER(Problem), vp, vp, i32, i32, vp, vp, vp]
@@ -144,7 +148,7 @@ def _declare(lib):
                  'mc_loss_reduce_backward', 'plan_amis_forward', 'plan_amis_backward', 'plan_evaluate_cost',
                  'monte_carlo_forward_diag', 'weight_stats', 'rslm_solve_diag', 'posterior_summary', 'posterior_resample',
                  'posterior_modes', 'amis_forward_costs', 'monte_carlo_forward_costs', 'amis_backward_costs',
-                 'amis_backward_split_costs', 'request_sample_costs', 'pose_errors'):
+                 'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -165,7 +169,7 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_posterior_summary', 'epropnp_posterior_resample', 'epropnp_posterior_modes',
            'epropnp_amis_forward_costs', 'epropnp_monte_carlo_forward_costs', 'epropnp_amis_backward_costs',
            'epropnp_amis_backward_split_costs', 'epropnp_request_sample_costs', 'epropnp_pose_errors',
-           'epropnp_pose_errors_scratch_bytes')
+           'epropnp_pose_errors_scratch_bytes', 'epropnp_bev_overlap', 'epropnp_bev_nms', 'epropnp_bev_nms_scratch_bytes')
 
 
 def lib():

@@ -315,6 +315,47 @@ int epropnp_pose_errors(const float* pose_est /* (R,B,P), R >= 1 */, const float
                         float* errors /* (R,B,8) */, void* stream);
 size_t epropnp_pose_errors_scratch_bytes(int32_t num_rows_per_obj, int32_t num_obj, int32_t max_model_points);
 
+/* Rotated bird's-eye-view boxes: overlap area / IoU and the grouped greedy non-maximum suppression the detection head ends with
+ * (EPro-PnP-Det core/bbox_3d/misc.py:300-324 batched_bev_nms and nuscenes3d_dataset.py:395 nms_gpu, there through the CUDA extension
+ * ops/iou3d, whose suppression mask is copied to the host and reduced in a C++ loop).
+ * A box is five floats (cx, cy, dx, dy, angle); its corners are (cx + u cos a + v sin a, cy - u sin a + v cos a) for u = +-dx/2,
+ * v = +-dy/2 -- the yaw convention of the 4-DoF pose with (x, z) as the plane, and the reference's rotate_around_center applied to
+ * its (x1, y1, x2, y2, ry) boxes.  A box is valid iff all five numbers are finite and dx >= 0, dy >= 0.
+ * One fp32 overlap routine serves every entry: A's corners in B's frame (relative to B's centre, half axes turned by
+ * angle_A - angle_B), then | sum over A's edges of the integral of clamp(y, -dy_B/2, dy_B/2) dx over the edge's part inside
+ * |x| <= dx_B/2 |, each edge by the trapezoid rule on its three linear pieces.  No collected intersection points, no margins: the
+ * result is continuous in the ten inputs.  The angle difference is reduced by the single constant fl(pi/2): identical boxes, a box
+ * against itself turned by k fl(pi/2), boxes sharing an edge or a corner, a zero-width box and distant boxes give exactly the area /
+ * exactly 0.  iou = overlap / max(area_a + area_b - overlap, 1e-8).
+ *
+ * epropnp_bev_overlap: out (num_a, num_b), or (num_a,) with aligned != 0 (which needs num_a == num_b: out[i] of boxes_a[i] and
+ * boxes_b[i], the bits of the pairwise call's diagonal), holds the overlap area (want_iou == 0) or the IoU.  NaN exactly where either
+ * box is invalid; every element is written.  One launch of 64 x 64 tiles (EPROPNP_BEV_TILE), both tiles' boxes staged in LDS in
+ * prepared form.  num_a == 0 or num_b == 0 launches nothing and follows no pointer.  EPROPNP_EINVAL: a negative count, aligned with
+ * num_a != num_b, a NULL pointer, num_a beyond 65535 tiles.
+ *
+ * epropnp_bev_nms: greedy suppression in the caller's visiting order.  order (N,) holds box indices, by descending score for the
+ * usual use; an entry outside [0, N) is a position without a box: it is skipped and nothing is read out of bounds.  Walking `order`,
+ * a valid box that is not yet suppressed is kept, and then suppresses every LATER box of the same group (group[i], all one group
+ * with group == NULL) whose IoU with it is > iou_thr -- strictly, as in the reference.  Boxes of different groups never interact (no
+ * coordinate is shifted to keep them apart); an invalid box is not kept and suppresses nothing.  Outputs, every element written:
+ * keep_index (N,) the kept indices in visiting order, then -1; keep_mask (N,) 1 / 0 by box index; num_keep (1,).
+ * Two launches on `stream`, no cross-workgroup waiting, no atomics, no host synchronisation: (1) one wave per 64 x 64 tile of the
+ * visiting order, column tile >= row tile, writes one 64-bit word per row and tile into scratch -- pairs of different groups and
+ * pairs whose centres are further apart than the sum of the half diagonals are rejected before the overlap arithmetic; (2) one
+ * workgroup walks the row tiles with the `removed` bitset in LDS.  Two calls agree to the last bit.  scratch: at least
+ * epropnp_bev_nms_scratch_bytes(N) = N * ceil(N / 64) * 8 bytes (the mask; the reduce launch needs nothing beyond it).
+ * num_boxes == 0 launches the reduce kernel alone, which writes num_keep[0] = 0 (boxes, order, scratch, keep_index and keep_mask are
+ * not followed).  EPROPNP_EINVAL: num_boxes < 0 or above 262144, scratch_bytes below the size query, a NULL num_keep, a NULL boxes /
+ * order / scratch / keep_index / keep_mask with num_boxes > 0.  Capturable into a hipGraph. */
+#define EPROPNP_BEV_TILE 64   /* boxes per tile edge: one mask word per row and column tile */
+int epropnp_bev_overlap(const float* boxes_a /* (num_a,5) */, int32_t num_a, const float* boxes_b /* (num_b,5) */, int32_t num_b,
+                        int32_t want_iou, int32_t aligned, float* out /* (num_a,num_b) or (num_a,) */, void* stream);
+size_t epropnp_bev_nms_scratch_bytes(int32_t num_boxes);
+int epropnp_bev_nms(const float* boxes /* (N,5) */, const int32_t* order /* (N,) */, const int32_t* group /* (N,) or NULL */,
+                    int32_t num_boxes, float iou_thr, void* scratch, size_t scratch_bytes, int32_t* keep_index /* (N,) */,
+                    uint8_t* keep_mask /* (N,) */, int32_t* num_keep /* (1,) */, void* stream);
+
 int epropnp_abi_version(void);
 const char* epropnp_last_error(void);
 
@@ -322,7 +363,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
