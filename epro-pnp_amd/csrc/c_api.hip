@@ -246,6 +246,33 @@ int epropnp_bev_nms(const float* boxes, const int32_t* order, const int32_t* gro
                              (hipStream_t)stream);
 }
 
+size_t epropnp_orient_density_scratch_bytes(int32_t mc_samples, int32_t num_obj) {
+  return pnp::orient_density_scratch_bytes(mc_samples, num_obj);
+}
+
+int epropnp_orient_density(const float* pose_samples, const float* logweights, const float* pose_opt, int32_t mc_samples,
+                           int32_t num_obj, int32_t dof, int32_t size, int32_t window_h, int32_t window_w, float saturation,
+                           float sphere_opacity, float intensity_scale, void* scratch, size_t scratch_bytes, float* image,
+                           float* front, float* back, int32_t* bins, void* stream) {
+  pnp::StageScope prof_("orient_density", (hipStream_t)stream);
+  return pnp::launch_orient_density(pose_samples, logweights, pose_opt, mc_samples, num_obj, dof, size, window_h, window_w, saturation,
+                                    sphere_opacity, intensity_scale, scratch, scratch_bytes, image, front, back, bins,
+                                    (hipStream_t)stream);
+}
+
+size_t epropnp_bev_density_scratch_bytes(int32_t mc_samples, int32_t num_obj) {
+  return pnp::bev_density_scratch_bytes(mc_samples, num_obj);
+}
+
+int epropnp_bev_density(const float* pose_samples, const float* logweights, const float* obj_weight, const int32_t* obj_offsets,
+                        int32_t mc_samples, int32_t num_obj, int32_t num_groups, int32_t dof, int32_t height, int32_t width,
+                        float scale, int32_t origin_x, int32_t origin_y, int32_t window, void* scratch, size_t scratch_bytes,
+                        float* density, int32_t* bins, void* stream) {
+  pnp::StageScope prof_("bev_density", (hipStream_t)stream);
+  return pnp::launch_bev_density(pose_samples, logweights, obj_weight, obj_offsets, mc_samples, num_obj, num_groups, dof, height,
+                                 width, scale, origin_x, origin_y, window, scratch, scratch_bytes, density, bins, (hipStream_t)stream);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);

@@ -292,6 +292,16 @@ int launch_bev_overlap(const float* boxes_a, int M, const float* boxes_b, int N,
 int launch_bev_nms(const float* boxes, const int32_t* order, const int32_t* group, int N, float thr, void* scratch,
                    size_t scratch_bytes, int32_t* keep_index, uint8_t* keep_mask, int32_t* num_keep, hipStream_t st);
 size_t bev_nms_scratch_bytes(int N);
+// density_kernels.hip: density pictures of the weighted pose samples (epropnp_orient_density, epropnp_bev_density): one launch that
+// turns samples into weighted bins, one that sums them per 32 x 32 tile in LDS, box-filters and writes the picture
+int launch_orient_density(const float* pose, const float* logw, const float* pose_opt, int S, int B, int dof, int size, int kh,
+                          int kw, float saturation, float opacity, float intensity, void* scratch, size_t scratch_bytes,
+                          float* image, float* front, float* back, int32_t* bins, hipStream_t st);
+int launch_bev_density(const float* pose, const float* logw, const float* obj_weight, const int32_t* offsets, int S, int B, int G,
+                       int dof, int H, int W, float scale, int ox, int oy, int window, void* scratch, size_t scratch_bytes,
+                       float* density, int32_t* bins, hipStream_t st);
+size_t orient_density_scratch_bytes(int S, int B);
+size_t bev_density_scratch_bytes(int S, int B);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

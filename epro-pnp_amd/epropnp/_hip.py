@@ -102,6 +102,12 @@ def _declare(lib):
     lib.epropnp_bev_nms.argtypes = [vp, vp, vp, i32, C.c_float, vp, C.c_size_t, vp, vp, vp, vp]
     lib.epropnp_bev_nms_scratch_bytes.argtypes = [i32]
     lib.epropnp_bev_nms_scratch_bytes.restype = C.c_size_t
+    f32 = C.c_float
+    lib.epropnp_orient_density.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    lib.epropnp_bev_density.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
+    for name in ('orient', 'bev'):
+        getattr(lib, f'epropnp_{name}_density_scratch_bytes').argtypes = [i32, i32]
+        getattr(lib, f'epropnp_{name}_density_scratch_bytes').restype = C.c_size_t
     lib.epropnp_evaluate_cost.argtypes = [C.POINTER(Problem), vp, i32, vp, vp]
     lib.epropnp_normal_equations.argtypes = [C.POINTER(Problem), vp, i32, vp, vp, vp, vp]
     lib.epropnp_cost_pose_cam_grad.argtypes = [C.POINTER(Problem), vp, vp, i32, i32, vp, vp, vp]
@@ -148,7 +154,8 @@ def _declare(lib):
                  'mc_loss_reduce_backward', 'plan_amis_forward', 'plan_amis_backward', 'plan_evaluate_cost',
                  'monte_carlo_forward_diag', 'weight_stats', 'rslm_solve_diag', 'posterior_summary', 'posterior_resample',
                  'posterior_modes', 'amis_forward_costs', 'monte_carlo_forward_costs', 'amis_backward_costs',
-                 'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms'):
+                 'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms', 'orient_density',
+                 'bev_density'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -169,7 +176,9 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_posterior_summary', 'epropnp_posterior_resample', 'epropnp_posterior_modes',
            'epropnp_amis_forward_costs', 'epropnp_monte_carlo_forward_costs', 'epropnp_amis_backward_costs',
            'epropnp_amis_backward_split_costs', 'epropnp_request_sample_costs', 'epropnp_pose_errors',
-           'epropnp_pose_errors_scratch_bytes', 'epropnp_bev_overlap', 'epropnp_bev_nms', 'epropnp_bev_nms_scratch_bytes')
+           'epropnp_pose_errors_scratch_bytes', 'epropnp_bev_overlap', 'epropnp_bev_nms', 'epropnp_bev_nms_scratch_bytes',
+           'epropnp_orient_density', 'epropnp_orient_density_scratch_bytes', 'epropnp_bev_density',
+           'epropnp_bev_density_scratch_bytes')
 
 
 def lib():

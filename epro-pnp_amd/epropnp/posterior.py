@@ -5,6 +5,8 @@ The layer's product is a pose distribution in its raw form: `pose_samples (S,B,4
 reduce launches over (S,B,.) temporaries -- the Det head's test-time orientation score and the moments of the distribution;
 `resample` turns it into equally weighted draws (systematic resampling) for a tracker or planner; `modes` finds the hypotheses of
 an ambiguous posterior -- the peaks, their probability mass and the samples that belong to each (quick-shift clustering).
+`orient_density` and `bev_density` draw it: the orientation sphere of the 6-DoF test loop and the bird's-eye-view sample density of
+the Det detector, splat + box filter (+ colour composite) without a full-canvas temporary or a float atomic.
 
 All run on the current HIP stream of the inputs' device, allocate their outputs with torch.empty, never synchronise and can be
 captured into a hipGraph.  None is differentiable: inputs are detached.
@@ -154,3 +156,128 @@ def modes(pose_samples, pose_sample_logweights, bandwidth, max_modes=4, link=3.0
                   _hip.ptr(out.parent), _hip.ptr(out.labels), _hip.ptr(out.num_modes), _hip.ptr(out.index), _hip.ptr(out.mass),
                   _hip.ptr(out.poses), _hip.stream_of(ps))
     return out
+
+
+OrientDensity = namedtuple('OrientDensity', ['image', 'front', 'back', 'bins'])
+OrientDensity.__doc__ = """Orientation-sphere picture of the weighted 6-DoF pose samples (include/epropnp_hip.h: epropnp_orient_density).
+
+image (B,size,size,3)   the colour composite of the reference's `draw_orient_density`, in [0, 1]
+front (B,size,size,3)   box-summed weight of rotated axis k on the front hemisphere (a_z <= 0); None unless with_density
+back  (B,size,size,3)   the same on the back hemisphere; None unless with_density
+bins  (S,B,3) int32     the bin each axis point fell into: py * size + px, + size^2 on the back hemisphere, -1 when dropped;
+                        None unless with_bins"""
+
+BevDensity = namedtuple('BevDensity', ['density', 'bins'])
+BevDensity.__doc__ = """Bird's-eye-view density of the weighted pose samples (include/epropnp_hip.h: epropnp_bev_density).
+
+density (G,H,W)       box-summed weight per grid cell and group
+bins    (S,B) int32   the cell each sample fell into: py * W + px, -1 when off the grid; None unless with_bins"""
+
+
+def _window(window, name):
+    kh, kw = (window, window) if isinstance(window, int) else tuple(window)
+    kh, kw = int(kh), int(kw)
+    for k in (kh, kw):
+        if k < 1 or k > 9 or k % 2 == 0:
+            raise ValueError(f'{name}: odd sizes from 1 to 9 are expected, got {window}')
+    return kh, kw
+
+
+def orient_density(pose_samples, pose_sample_logweights, pose_opt=None, size=512, window=(5, 5), saturation=0.5,
+                   sphere_opacity=0.6, intensity_scale=50, with_density=False, with_bins=False):
+    """Orientation-sphere density of 6-DoF pose samples -> OrientDensity: the arithmetic of the reference's
+    `draw_orient_density` (EPro-PnP-6DoF lib/utils/draw_orient_density.py) in two launches, without a full-canvas temporary.
+
+    Per object the weights are softmax(logweights) over the samples; sample j puts weight w_j for axis k at the pixel
+    rint(a * 0.4 size + size / 2 - 0.5) of a = column k of its quaternion's rotation (not normalised), on the front canvas iff
+    a_z <= 0; points off the canvas or not finite are dropped.  front / back are the zero-padded (kh, kw) box sums; the image is
+    (back_layer * opacity + circle * (1 - opacity)) * front_layer with layer_c = prod_k col[k, c] ** (intensity_scale * density_k).
+    pose_opt (B,7): its three axes are drawn as lines from the centre -- a pixel whose centre lies within 1.5 px of the segment
+    takes the axis' pure colour, a later axis over an earlier one (the reference's cv2.line(thickness=3) is not reproduced pixel
+    for pixel).  A column holding a NaN / +inf log-weight or nothing but -inf gives a NaN canvas.  Every sum runs in sample order:
+    two calls agree to the last bit."""
+    ps, lw, dof = _inputs(pose_samples, pose_sample_logweights)
+    if dof != 6:
+        raise ValueError('orient_density shows orientations: pose_samples (S,B,7) expected')
+    S, B, P = ps.shape
+    size = int(size)
+    if size < 1 or size > 4096:
+        raise ValueError(f'size must be 1 .. 4096, got {size}')
+    kh, kw = _window(window, 'window')
+    opt = None
+    if pose_opt is not None:
+        opt = _f32c(pose_opt, 'pose_opt')
+        if opt.shape != (B, P):
+            raise ValueError(f'pose_opt: expected {(B, P)}, got {tuple(opt.shape)}')
+    dev = ps.device
+    image = torch.empty((B, size, size, 3), dtype=torch.float32, device=dev)
+    front = torch.empty((B, size, size, 3), dtype=torch.float32, device=dev) if with_density else None
+    back = torch.empty((B, size, size, 3), dtype=torch.float32, device=dev) if with_density else None
+    bins = torch.empty((S, B, 3), dtype=torch.int32, device=dev) if with_bins else None
+    if B > 0:
+        nbytes = int(_hip.lib().epropnp_orient_density_scratch_bytes(S, B))
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _hip.call('epropnp_orient_density', _hip.ptr(ps), _hip.ptr(lw), _hip.ptr(opt), S, B, dof, size, kh, kw, float(saturation),
+                  float(sphere_opacity), float(intensity_scale), _hip.ptr(scratch), nbytes, _hip.ptr(image), _hip.ptr(front),
+                  _hip.ptr(back), _hip.ptr(bins), _hip.stream_of(ps))
+    return OrientDensity(image=image, front=front, back=back, bins=bins)
+
+
+def bev_density(pose_samples, pose_sample_logweights, height, width, scale=10., origin=None, obj_weight=None, groups=None,
+                num_groups=None, window=3, with_bins=False):
+    """Bird's-eye-view density of the pose samples of many objects -> BevDensity: the density block of the reference's `show_bev`
+    (EPro-PnP-Det core/visualizer/image_bev_vis.py:79-95) on the device.
+
+    Sample j of object b adds softmax(logweights[:, b])_j * obj_weight[b] (the 2-D score; 1 without) at px = rint(z * scale) +
+    origin[0], py = rint(x * scale) + origin[1] of the grid of its group (`groups` (B,) integers in [0, num_groups), e.g. the image
+    index; one group without; objects of a group outside that range are left out); origin=None is (int(width / 16),
+    int(height / 2)) as in `show_bev`.  Samples off the grid are dropped, an object with a bad column adds nothing.  density is the
+    zero-padded window x window box sum -- cv2.blur times window^2, except in the outermost window // 2 rows and columns, where
+    cv2.blur reflects.  Objects need not be sorted by group; with `groups` given pass `num_groups` too, or it is read off the
+    device (groups.max() + 1: one synchronisation)."""
+    ps, lw, dof = _inputs(pose_samples, pose_sample_logweights)
+    S, B, P = ps.shape
+    H, W = int(height), int(width)
+    if H < 1 or H > 4096 or W < 1 or W > 4096:
+        raise ValueError(f'height and width must be 1 .. 4096, got {height} and {width}')
+    if not isinstance(window, int):
+        raise ValueError(f'window: one odd size from 1 to 9 is expected, got {window}')
+    k, _ = _window(window, 'window')
+    ox, oy = (int(W / 16), int(H / 2)) if origin is None else (int(origin[0]), int(origin[1]))
+    dev = ps.device
+    ow = None
+    if obj_weight is not None:
+        ow = _f32c(obj_weight, 'obj_weight')
+        if ow.shape != (B,):
+            raise ValueError(f'obj_weight: expected {(B,)}, got {tuple(ow.shape)}')
+    perm = None
+    if groups is None:
+        G = 1 if num_groups is None else int(num_groups)
+        offsets = torch.zeros((G + 1,), dtype=torch.int32, device=dev)
+        if G > 0:
+            offsets[1:] = B
+    else:
+        if not torch.is_tensor(groups) or groups.dtype not in (torch.int32, torch.int64) or groups.shape != (B,):
+            raise ValueError(f'groups: a ({B},) integer tensor is expected')
+        _hip.check_device(groups, 'groups')
+        if groups.device != dev:
+            raise RuntimeError(f'groups lives on {groups.device}, the samples on {dev}')
+        G = int(num_groups) if num_groups is not None else (int(groups.max().item()) + 1 if B > 0 else 0)
+        sorted_groups, perm = torch.sort(groups.detach().to(torch.int64), stable=True)
+        offsets = torch.searchsorted(sorted_groups, torch.arange(G + 1, dtype=torch.int64, device=dev)).to(torch.int32)
+        ps, lw = ps[:, perm].contiguous(), lw[:, perm].contiguous()
+        ow = None if ow is None else ow[perm].contiguous()
+    if G < 0:
+        raise ValueError(f'num_groups must be >= 0, got {num_groups}')
+    density = torch.empty((G, H, W), dtype=torch.float32, device=dev)
+    bins = torch.empty((S, B), dtype=torch.int32, device=dev) if with_bins else None
+    if G > 0 or (B > 0 and with_bins):
+        nbytes = int(_hip.lib().epropnp_bev_density_scratch_bytes(S, B))
+        scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+        _hip.call('epropnp_bev_density', _hip.ptr(ps), _hip.ptr(lw), _hip.ptr(ow), _hip.ptr(offsets), S, B, G, dof, H, W, float(scale),
+                  ox, oy, k, _hip.ptr(scratch), nbytes, _hip.ptr(density), _hip.ptr(bins), _hip.stream_of(ps))
+    if bins is not None and perm is not None:
+        unsorted = torch.empty_like(bins)
+        unsorted[:, perm] = bins
+        bins = unsorted
+    return BevDensity(density=density, bins=bins)

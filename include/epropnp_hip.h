@@ -356,6 +356,59 @@ int epropnp_bev_nms(const float* boxes /* (N,5) */, const int32_t* order /* (N,)
                     int32_t num_boxes, float iou_thr, void* scratch, size_t scratch_bytes, int32_t* keep_index /* (N,) */,
                     uint8_t* keep_mask /* (N,) */, int32_t* num_keep /* (1,) */, void* stream);
 
+/* Density pictures of the posterior, the weighted pose samples (S,B,P) + log-weights (S,B).  Both entries are one primitive -- a list
+ * of weighted points (canvas, plane, pixel, weight) summed into pixels, then a zero-padded box sum of odd size -- in two launches:
+ * one workgroup per object turns its samples into weights and bins; one workgroup per (canvas, 32 x 32 pixel tile) sums the points
+ * that fall into tile + halo in LDS, each pixel in sample order, box-sums and writes the outputs.  No floating-point atomics: two
+ * calls agree to the last bit.  Every output element is written.  No allocation, no synchronisation; capturable into a hipGraph.
+ * Weights, per object b: w_j = exp(logw[j,b] - max_j logw[:,b]) / sum_j exp(..), one rounding in the exponent's argument, as
+ * epropnp_posterior_summary.  A bad column holds a NaN / +inf log-weight or nothing but -inf.
+ *
+ * epropnp_orient_density (EPro-PnP-6DoF lib/utils/draw_orient_density.py:10-73, called at lib/test.py:219-225): dof must be 6.
+ * Sample j of object b gives three points, one per plane k: a = column k of the rotation matrix of its quaternion [w,x,y,z], taken
+ * as it is (the reference's `axisrot`; not normalised);  px = rint(a_x * (0.4 size) + (size / 2 - 0.5)), py likewise from a_y, round
+ * half to even as torch.round;  front hemisphere iff a_z <= 0.  A point off the canvas or with a coordinate that is not finite is
+ * dropped (the reference would raise).  front[b,y,x,k] / back[b,y,x,k] = sum of w_j over the points of plane k whose pixel lies in the
+ * (window_h, window_w) window about (y, x): the reference's avg_pool2d(..) * kh * kw without intensity_scale.  image[b,y,x,c] =
+ * (back_layer * sphere_opacity + circle * (1 - sphere_opacity)) * front_layer with layer_c = prod_k col[k,c] ^ (intensity_scale *
+ * density_k), col = eye(3) * saturation + (1 - saturation) / 2, circle = 1 - 0.5 [((x - c) / r)^2 + ((y - c) / r)^2 <= 1],
+ * c = size / 2 - 0.5, r = 0.4 size.  pose_opt (num_obj,7) or NULL: its three axes as lines from the centre to their projections,
+ * drawn onto the bracket before the multiplication by front_layer -- a pixel whose centre lies within 1.5 px of segment k takes the
+ * pure colour of axis k, a later axis over an earlier one (our rule in place of cv2.line(thickness=3, shift=3); OpenCV's rasteriser is
+ * not reproduced pixel for pixel).  An object with a bad column: front, back and image are NaN everywhere.
+ * bins (S,B,3) int32: py * size + px, + size^2 on the back hemisphere, -1 when dropped; the geometry alone decides it.
+ * image, front, back, bins: each may be NULL (not wanted), not all four.  num_obj == 0 launches nothing and follows no pointer.
+ * EPROPNP_EINVAL: num_obj < 0 or > 65535, dof != 6, mc_samples < 1, size outside 1 .. 4096, a window that is even or outside 1 .. 9, a
+ * NULL pose_samples / logweights / scratch or four NULL outputs with num_obj > 0, scratch_bytes below the size query.
+ *
+ * epropnp_bev_density (EPro-PnP-Det core/visualizer/image_bev_vis.py:79-95 show_bev, fed by deform_pnp_head.py:554-598 and
+ * detectors/epropnp_det.py:118-126): dof 4 or 6, only the translation is read.  Objects are sorted by group: group g owns the objects
+ * obj_offsets[g] .. obj_offsets[g+1] - 1 (obj_offsets (num_groups + 1,), clamped into [0, num_obj]; offsets that do not ascend are not
+ * detected: such a group is empty).  Sample j of object b adds w_j * obj_weight[b] (1 with obj_weight == NULL) at px = rint(z * scale)
+ * + origin_x, py = rint(x * scale) + origin_y -- the reference's proj_mat = [[0, scale], [scale, 0]].  Samples off the grid are
+ * dropped; an object with a bad column adds nothing.  density (num_groups, height, width): the zero-padded window x window box sum,
+ * i.e. cv2.blur * window^2 except in the outermost window / 2 rows and columns, where cv2.blur reflects at the border.
+ * bins (S,B) int32: py * width + px, -1 when dropped.  May be NULL.
+ * num_groups == 0: density is not followed; num_obj == 0: every density element is 0 and no sample pointer is followed.
+ * EPROPNP_EINVAL: a negative count, num_groups > 65535, dof not 4 or 6, mc_samples < 1, height or width outside 1 .. 4096, a window
+ * that is even or outside 1 .. 9, a NULL pose_samples / logweights / scratch with num_obj > 0, a NULL obj_offsets / density with
+ * num_groups > 0, scratch_bytes below the size query.
+ *
+ * scratch: at least epropnp_*_density_scratch_bytes(mc_samples, num_obj) = num_obj * 32 + mc_samples * num_obj * 4 * (1 + K) bytes
+ * (K = 3 points per sample for the sphere, 1 for the grid): per-object bounding boxes, the weights and the bins. */
+size_t epropnp_orient_density_scratch_bytes(int32_t mc_samples, int32_t num_obj);
+int epropnp_orient_density(const float* pose_samples /* (S,B,7) */, const float* logweights /* (S,B) */,
+                           const float* pose_opt /* (B,7) or NULL */, int32_t mc_samples, int32_t num_obj, int32_t dof, int32_t size,
+                           int32_t window_h, int32_t window_w, float saturation, float sphere_opacity, float intensity_scale,
+                           void* scratch, size_t scratch_bytes, float* image /* (B,size,size,3) */, float* front /* (B,size,size,3) */,
+                           float* back /* (B,size,size,3) */, int32_t* bins /* (S,B,3) */, void* stream);
+size_t epropnp_bev_density_scratch_bytes(int32_t mc_samples, int32_t num_obj);
+int epropnp_bev_density(const float* pose_samples /* (S,B,4|7) */, const float* logweights /* (S,B) */,
+                        const float* obj_weight /* (B,) or NULL */, const int32_t* obj_offsets /* (G+1,) */, int32_t mc_samples,
+                        int32_t num_obj, int32_t num_groups, int32_t dof, int32_t height, int32_t width, float scale, int32_t origin_x,
+                        int32_t origin_y, int32_t window, void* scratch, size_t scratch_bytes, float* density /* (G,H,W) */,
+                        int32_t* bins /* (S,B) */, void* stream);
+
 int epropnp_abi_version(void);
 const char* epropnp_last_error(void);
 
@@ -363,7 +416,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "orient_density", "bev_density") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
