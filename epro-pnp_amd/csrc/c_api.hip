@@ -273,6 +273,33 @@ int epropnp_bev_density(const float* pose_samples, const float* logweights, cons
                                  width, scale, origin_x, origin_y, window, scratch, scratch_bytes, density, bins, (hipStream_t)stream);
 }
 
+int epropnp_deform_sample_forward(const float* query, const float* key, const float* value, const float* dense_x2d,
+                                  const float* dense_mask, const float* sampling_location, const int64_t* obj_img_ind,
+                                  int32_t num_obj, int32_t num_img, int32_t num_heads, int32_t num_points, int32_t head_dim,
+                                  int32_t height, int32_t width, int32_t stride, int64_t stride_n, int64_t stride_c,
+                                  int64_t stride_h, int64_t stride_w, float* attn, float* v_samples, float* a_samples,
+                                  float* mask_samples, float* x2d_samples, float* stats, void* stream) {
+  pnp::StageScope prof_("deform_sample_forward", (hipStream_t)stream);
+  return pnp::launch_deform_forward(query, key, value, dense_x2d, dense_mask, sampling_location, (const long long*)obj_img_ind, num_obj,
+                                    num_img, num_heads, num_points, head_dim, height, width, stride, stride_n, stride_c, stride_h,
+                                    stride_w, attn, v_samples, a_samples, mask_samples, x2d_samples, stats, (hipStream_t)stream);
+}
+
+int epropnp_deform_sample_backward(const float* query, const float* key, const float* value, const float* dense_x2d,
+                                   const float* dense_mask, const float* sampling_location, const int64_t* obj_img_ind,
+                                   const float* stats, const float* grad_attn, const float* grad_v_samples,
+                                   const float* grad_a_samples, const float* grad_mask_samples, const float* grad_x2d_samples,
+                                   int32_t num_obj, int32_t num_img, int32_t num_heads, int32_t num_points, int32_t head_dim,
+                                   int32_t height, int32_t width, int32_t stride, int64_t stride_n, int64_t stride_c,
+                                   int64_t stride_h, int64_t stride_w, float* grad_query, float* grad_key, float* grad_value,
+                                   float* grad_location, void* stream) {
+  pnp::StageScope prof_("deform_sample_backward", (hipStream_t)stream);
+  return pnp::launch_deform_backward(query, key, value, dense_x2d, dense_mask, sampling_location, (const long long*)obj_img_ind, stats,
+                                     grad_attn, grad_v_samples, grad_a_samples, grad_mask_samples, grad_x2d_samples, num_obj, num_img,
+                                     num_heads, num_points, head_dim, height, width, stride, stride_n, stride_c, stride_h, stride_w,
+                                     grad_query, grad_key, grad_value, grad_location, (hipStream_t)stream);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);

@@ -302,6 +302,17 @@ int launch_bev_density(const float* pose, const float* logw, const float* obj_we
                        float* density, int32_t* bins, hipStream_t st);
 size_t orient_density_scratch_bytes(int S, int B);
 size_t bev_density_scratch_bytes(int S, int B);
+// deform_kernels.hip: the detection head's deformable attention sampler (epropnp_deform_sample_forward / _backward): one launch each,
+// one wave per (object, head); the backward zero-fills the map gradients it is given and scatters into them with float atomics
+int launch_deform_forward(const float* query, const float* key, const float* value, const float* x2d, const float* mask,
+                          const float* loc, const long long* img, int B, int NI, int H, int P, int D, int h, int w, int stride,
+                          long long sN, long long sC, long long sH, long long sW, float* attn, float* v_out, float* a_out,
+                          float* m_out, float* x_out, float* stats, hipStream_t st);
+int launch_deform_backward(const float* query, const float* key, const float* value, const float* x2d, const float* mask,
+                           const float* loc, const long long* img, const float* stats, const float* g_attn, const float* g_v,
+                           const float* g_a, const float* g_m, const float* g_x, int B, int NI, int H, int P, int D, int h, int w,
+                           int stride, long long sN, long long sC, long long sH, long long sW, float* dq, float* dkey,
+                           float* dvalue, float* dloc, hipStream_t st);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

@@ -675,6 +675,45 @@ int epropnp_prepare_dense_backward(const float* noc_map, const float* dim, const
                                    float* grad_noc_map, float* grad_dim, float* grad_logit_map, float* grad_scale,
                                    void* stream);
 
+/* The deformable attention sampler of the detection head, fused (EPro-PnP-Det epropnp_det/ops/deformable_attention_sampler.py:77-137,
+ * called from deform_pnp_head.py:447-451).  Per object b, head j, point p, with image i = obj_img_ind[b]:
+ *   px = x / stride - 0.5, py = y / stride - 0.5           :84-93: the normalise / un-normalise round trip, align_corners=False
+ *   k, v, x2d : bilinear, border padding (px, py clamped to the map)        :96-121     head j reads channels j*D .. j*D+D-1
+ *   mask      : bilinear, zero padding (no clamp)                             :122-128
+ *   a_samples = q . k / sqrt(D)                                               :131
+ *   attn      = sum_p v_p softmax_P(a)_p mask_p                               :132-137   (what the reference feeds to out_proj)
+ * query (B,H,D), key / value (NI, H*D, h, w) read through the element strides (stride_n, stride_c, stride_h, stride_w) -- contiguous
+ * NCHW or channels-last without a copy; channels-last is the fast layout (one corner of one head is D contiguous floats) --,
+ * dense_x2d (NI,2,h,w) and dense_mask (NI,1,h,w) contiguous, sampling_location (B,H,P,2) input-image pixels [x, y], obj_img_ind (B,)
+ * int64, `stride` the map's stride
+ *   -> attn (B,H*D), v_samples (B,H,P,D) POINT-major (the reference's (B,H,D,P) is its transposed view), a_samples (B,H,P),
+ *      mask_samples (B,H,P), x2d_samples (B,H,P,2) point-major, stats (B,H,2) = {max_p a, sum_p exp(a - max)} kept for the backward.
+ * Memory safety is part of the semantics -- no input value forms an out-of-range address: corner indices are clamped as integers
+ * after the conversion; a NaN location samples the border-mode maps at coordinate 0 and a huge one at the clamped coordinate, both
+ * give mask_samples = 0 and a zero location gradient along that axis; obj_img_ind is clamped to [0, NI - 1] on the device (a host check would
+ * synchronise).  One launch, no allocation, no synchronisation; capturable into a hipGraph.  num_obj == 0 launches nothing.
+ * EPROPNP_EINVAL: num_points or head_dim outside 1 .. 64, num_heads / num_img / height / width / stride < 1, a stride below 1 or
+ * strides that reach outside NI * H*D * h * w elements, a NULL pointer. */
+int epropnp_deform_sample_forward(const float* query, const float* key, const float* value, const float* dense_x2d,
+                                  const float* dense_mask, const float* sampling_location, const int64_t* obj_img_ind,
+                                  int32_t num_obj, int32_t num_img, int32_t num_heads, int32_t num_points, int32_t head_dim,
+                                  int32_t height, int32_t width, int32_t stride, int64_t stride_n, int64_t stride_c,
+                                  int64_t stride_h, int64_t stride_w, float* attn, float* v_samples, float* a_samples,
+                                  float* mask_samples, float* x2d_samples, float* stats, void* stream);
+/* Its backward.  Cotangents in the forward's layouts, NULL = absent: grad_attn (B,H*D), grad_v_samples (B,H,P,D), grad_a_samples
+ * (B,H,P), grad_mask_samples (B,H,P), grad_x2d_samples (B,H,P,2).  Gradients, NULL = not wanted: grad_query (B,H,D), grad_location
+ * (B,H,P,2) -- through k, v, x2d and the mask; zero along an axis on which the coordinate is clamped, as grid_sample's -- both
+ * summed in a fixed order; grad_key / grad_value: NI * H*D * h * w floats each with the maps' strides, zero-filled here and then
+ * scattered into with float atomics (their last bits depend on the arrival order).  dense_x2d, dense_mask get no gradient. */
+int epropnp_deform_sample_backward(const float* query, const float* key, const float* value, const float* dense_x2d,
+                                   const float* dense_mask, const float* sampling_location, const int64_t* obj_img_ind,
+                                   const float* stats, const float* grad_attn, const float* grad_v_samples,
+                                   const float* grad_a_samples, const float* grad_mask_samples, const float* grad_x2d_samples,
+                                   int32_t num_obj, int32_t num_img, int32_t num_heads, int32_t num_points, int32_t head_dim,
+                                   int32_t height, int32_t width, int32_t stride, int64_t stride_n, int64_t stride_c,
+                                   int64_t stride_h, int64_t stride_w, float* grad_query, float* grad_key, float* grad_value,
+                                   float* grad_location, void* stream);
+
 /* Backward of epropnp_shift_poses w.r.t. the pose (the offset is a constant, pnp_normalize detaches it):
  * grad_out (P,B,pose_len) -> grad_pose (P,B,pose_len). */
 int epropnp_shift_poses_backward(const float* pose, const float* offset, const float* grad_out, int32_t num_poses,
