@@ -300,6 +300,19 @@ int epropnp_deform_sample_backward(const float* query, const float* key, const f
                                      grad_query, grad_key, grad_value, grad_location, (hipStream_t)stream);
 }
 
+int epropnp_roi_logsumexp_forward(const float* roi_inputs, const float* rois, int32_t num_rois, int32_t channels, int32_t roi_height,
+                                  int32_t roi_width, float* out, void* stream) {
+  pnp::StageScope prof_("roi_logsumexp_forward", (hipStream_t)stream);
+  return pnp::launch_roi_logsumexp_forward(roi_inputs, rois, num_rois, channels, roi_height, roi_width, out, (hipStream_t)stream);
+}
+
+int epropnp_roi_logsumexp_backward(const float* roi_inputs, const float* rois, const float* out, const float* grad_out, int32_t num_rois,
+                                   int32_t channels, int32_t roi_height, int32_t roi_width, float* grad_inputs, void* stream) {
+  pnp::StageScope prof_("roi_logsumexp_backward", (hipStream_t)stream);
+  return pnp::launch_roi_logsumexp_backward(roi_inputs, rois, out, grad_out, num_rois, channels, roi_height, roi_width, grad_inputs,
+                                            (hipStream_t)stream);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);

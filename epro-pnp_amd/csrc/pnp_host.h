@@ -313,6 +313,11 @@ int launch_deform_backward(const float* query, const float* key, const float* va
                            const float* g_a, const float* g_m, const float* g_x, int B, int NI, int H, int P, int D, int h, int w,
                            int stride, long long sN, long long sC, long long sH, long long sW, float* dq, float* dkey,
                            float* dvalue, float* dloc, hipStream_t st);
+// roi_kernels.hip: the cross-RoI logsumexp of the detection head's auxiliary losses (epropnp_roi_logsumexp_forward / _backward): one
+// launch each, a workgroup per (RoI, channel); no atomics, every summation order fixed
+int launch_roi_logsumexp_forward(const float* x, const float* rois, int n, int c, int rh, int rw, float* out, hipStream_t st);
+int launch_roi_logsumexp_backward(const float* x, const float* rois, const float* out, const float* gout, int n, int c, int rh, int rw,
+                                  float* gx, hipStream_t st);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

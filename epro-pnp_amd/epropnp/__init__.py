@@ -1,5 +1,8 @@
 """MI355X-native EPro-PnP layer.  Same import surface as the reference's `epropnp` package
 (`from epropnp.epropnp import EProPnP6DoF`, ...); the LM solver and the AMIS sampler run as hand-written
 HIP kernels behind a C ABI (include/epropnp_hip.h).  Beyond that surface: `epropnp.deform`, the detection head's deformable
-attention sampler (the step that makes the correspondences) as one fused op and a drop-in module."""
+attention sampler (the step that makes the correspondences) as one fused op and a drop-in module, and `epropnp.roi`, the cross-RoI
+logsumexp / log-softmax / softmax of its auxiliary losses (the reference's `ops/inter_roi_ops.py`)."""
 from . import deform  # noqa: F401,E402
+from . import roi  # noqa: F401,E402
+from .roi import logsoftmax_across_rois, logsumexp_across_rois, softmax_across_rois  # noqa: F401,E402

@@ -111,6 +111,8 @@ def _declare(lib):
     i64 = C.c_int64
     lib.epropnp_deform_sample_forward.argtypes = [vp] * 7 + [i32] * 8 + [i64] * 4 + [vp] * 7
     lib.epropnp_deform_sample_backward.argtypes = [vp] * 13 + [i32] * 8 + [i64] * 4 + [vp] * 5
+    lib.epropnp_roi_logsumexp_forward.argtypes = [vp] * 2 + [i32] * 4 + [vp] * 2
+    lib.epropnp_roi_logsumexp_backward.argtypes = [vp] * 4 + [i32] * 4 + [vp] * 2
     lib.epropnp_evaluate_cost.argtypes = [C.POINTER(Problem), vp, i32, vp, vp]
     lib.epropnp_normal_equations.argtypes = [C.POINTER(Problem), vp, i32, vp, vp, vp, vp]
     lib.epropnp_cost_pose_cam_grad.argtypes = [C.POINTER(Problem), vp, vp, i32, i32, vp, vp, vp]
@@ -158,7 +160,8 @@ def _declare(lib):
                  'monte_carlo_forward_diag', 'weight_stats', 'rslm_solve_diag', 'posterior_summary', 'posterior_resample',
                  'posterior_modes', 'amis_forward_costs', 'monte_carlo_forward_costs', 'amis_backward_costs',
                  'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms', 'orient_density',
-                 'bev_density', 'deform_sample_forward', 'deform_sample_backward'):
+                 'bev_density', 'deform_sample_forward', 'deform_sample_backward', 'roi_logsumexp_forward',
+                 'roi_logsumexp_backward'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -181,7 +184,8 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_amis_backward_split_costs', 'epropnp_request_sample_costs', 'epropnp_pose_errors',
            'epropnp_pose_errors_scratch_bytes', 'epropnp_bev_overlap', 'epropnp_bev_nms', 'epropnp_bev_nms_scratch_bytes',
            'epropnp_orient_density', 'epropnp_orient_density_scratch_bytes', 'epropnp_bev_density',
-           'epropnp_bev_density_scratch_bytes', 'epropnp_deform_sample_forward', 'epropnp_deform_sample_backward')
+           'epropnp_bev_density_scratch_bytes', 'epropnp_deform_sample_forward', 'epropnp_deform_sample_backward',
+           'epropnp_roi_logsumexp_forward', 'epropnp_roi_logsumexp_backward')
 
 
 def lib():

@@ -101,3 +101,71 @@ class MonteCarloPoseLoss(nn.Module):
         if reduction != 'mean' or torch.is_tensor(avg_factor):
             return None
         return self.loss_weight / float(avg_factor)
+
+
+def mvd_gaussian_mixture_nll_loss(pred, target, logstd=None, logmixweight=None, rois=None, adaptive_weight=True, momentum=0.1,
+                                  mean_inv_std=None, dim=1, eps=1e-4, training=True):
+    """EPro-PnP-Det epropnp_det/models/losses/mvd_gaussian_mixture_nll_loss.py:15-63, element-wise (n, h, w): the negative log-likelihood
+    of a diagonal Gaussian mixture over the 2-D reprojection, pred / target / logstd (n, num_mix, h, w, 2), logmixweight
+    (n, num_mix, h, w); `target` a tensor, 0 (|pred| is the deviation) or -1 (pred is).  With `rois` (n, 5) the mixture log-likelihood
+    is summed across the RoIs of an image that cover the same position (epropnp.roi.logsumexp_across_rois: the fused kernels).  With
+    `adaptive_weight` the loss is divided by the running mean inverse standard deviation, updated in place while training (its batch
+    value is averaged over the process group when one is initialised)."""
+    if isinstance(target, int):
+        if target == 0:
+            diff = torch.abs(pred)
+        elif target == -1:
+            diff = pred
+        else:
+            raise ValueError(f'target must be a tensor, 0 or -1, got {target}')
+    else:
+        assert pred.size() == target.size() and target.numel() > 0
+        diff = torch.abs(pred - target)
+    inverse_std = torch.exp(-logstd).clamp(max=1 / eps)
+    diff_weighted_sq = (diff * inverse_std).square().sum(dim=-1)               # (n, num_mix, h, w)
+    loss_comp = -0.5 * diff_weighted_sq + logmixweight - logstd.sum(dim=-1)
+    if rois is None:
+        loss = torch.logsumexp(loss_comp, dim=dim).neg()
+    else:
+        from .roi import logsumexp_across_rois
+        loss = logsumexp_across_rois(torch.logsumexp(loss_comp, dim=dim, keepdim=True), rois).squeeze(1).neg()
+    if adaptive_weight:
+        if training:
+            with torch.no_grad():
+                mixweight = logmixweight.exp().unsqueeze(-1)
+                batch_mean_inv_std = _world_mean((inverse_std * mixweight).sum()) / _world_mean(mixweight.sum() * 2).clamp(min=eps)
+                mean_inv_std.mul_(1 - momentum).add_(momentum * batch_mean_inv_std)
+        loss = loss / mean_inv_std.clamp(min=eps)
+    return loss
+
+
+class MVDGaussianMixtureNLLLoss(nn.Module):
+    """The reference's module (mvd_gaussian_mixture_nll_loss.py:66-107): same constructor and forward signature; `rois=` goes through
+    **kwargs as there.  weight / avg_factor / reduction follow mmdet's `weighted_loss`: the weight multiplies element-wise, 'mean'
+    with an avg_factor is sum / avg_factor, 'sum' with an avg_factor raises."""
+
+    def __init__(self, dim=1, reduction='mean', loss_weight=1.0, adaptive_weight=True, momentum=0.1, eps=1e-4):
+        super().__init__()
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+        self.adaptive_weight = adaptive_weight
+        self.momentum = momentum
+        self.register_buffer('mean_inv_std', torch.tensor(1, dtype=torch.float))
+        self.dim = dim
+        self.eps = eps
+
+    def forward(self, pred, target, logstd=None, logmixweight=None, weight=None, avg_factor=None, reduction_override=None, **kwargs):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        loss = mvd_gaussian_mixture_nll_loss(pred, target, logstd=logstd, logmixweight=logmixweight, adaptive_weight=self.adaptive_weight,
+                                             momentum=self.momentum, mean_inv_std=self.mean_inv_std, dim=self.dim, eps=self.eps,
+                                             training=self.training, **kwargs)
+        if weight is not None:
+            loss = loss * weight
+        if avg_factor is None:
+            loss = loss.mean() if reduction == 'mean' else (loss.sum() if reduction == 'sum' else loss)
+        elif reduction == 'mean':
+            loss = loss.sum() / avg_factor
+        elif reduction != 'none':
+            raise ValueError('avg_factor can not be used with reduction="sum"')
+        return self.loss_weight * loss

@@ -714,6 +714,28 @@ int epropnp_deform_sample_backward(const float* query, const float* key, const f
                                    int64_t stride_h, int64_t stride_w, float* grad_query, float* grad_key, float* grad_value,
                                    float* grad_location, void* stream);
 
+/* The cross-RoI logsumexp of the detection head's auxiliary losses, fused (EPro-PnP-Det epropnp_det/ops/inter_roi_ops.py:19-81, called
+ * from deform_pnp_head.py:985 through logsoftmax_across_rois and from mvd_gaussian_mixture_nll_loss.py:50).  roi_inputs (n,c,rh,rw),
+ * rois (n,5) = [image id, x1, y1, x2, y2], id = round(rois[:,0]).  RoI j is a neighbour of i when j != i, id_j == id_i >= 0 and
+ * min(x2_i, x2_j) - max(x1_i, x1_j) > 0, the same in y (strict, in fp32: touching, empty and NaN boxes never pair)      :9-16, :31-43
+ *   X = x1_i + (px + 0.5) / rw * (x2_i - x1_i)                      the image position of cell (py, px) of RoI i; Y alike
+ *   gx = 2 (X - x1_j) / (x2_j - x1_j) - 1, valid = -1 < gx, gy < 1  :51-66, :71  (the overlap box of affine_mat cancels)
+ *   s_j = bilinear sample of roi_inputs[j, c] at u = clamp(((gx + 1) rw - 1) / 2, 0, rw - 1), v alike (border, align_corners=False)  :68
+ *   out[i,c,py,px] = log(exp(roi_inputs[i,c,py,px]) + sum over the neighbours j with valid: exp(s_j))                    :73-80
+ * computed in fp64 between the loads and the one rounding of out, with a running maximum (any magnitude of the inputs); a RoI
+ * without neighbours gets its input bits back.  Image ids and box corners only enter comparisons and the coordinate arithmetic: no
+ * value read from a tensor forms an address unchecked.  One launch, no allocation, no synchronisation; capturable into a hipGraph.
+ * num_rois == 0 or channels == 0 launches nothing.  EPROPNP_EINVAL: roi_height or roi_width < 1, roi_height * roi_width > 4096,
+ * num_rois * channels > 2^31 - 1, a NULL pointer. */
+int epropnp_roi_logsumexp_forward(const float* roi_inputs, const float* rois, int32_t num_rois, int32_t channels, int32_t roi_height,
+                                  int32_t roi_width, float* out, void* stream);
+/* Its backward w.r.t. roi_inputs (rois gets no gradient): `out` as the forward wrote it, grad_out (n,c,rh,rw) -> grad_inputs (n,c,rh,rw),
+ *   grad_inputs_j(q) = grad_out_j(q) exp(x_j(q) - out_j(q)) + sum over the i that have j as a neighbour, over their cells p with valid:
+ *                      grad_out_i(p) exp(s_j(p) - out_i(p)) wy(py, qy) wx(px, qx),   wx = max(0, 1 - |u(px) - qx|), wy alike.
+ * One launch, no float atomic, every summation order fixed: two launches give the same bits. */
+int epropnp_roi_logsumexp_backward(const float* roi_inputs, const float* rois, const float* out, const float* grad_out, int32_t num_rois,
+                                   int32_t channels, int32_t roi_height, int32_t roi_width, float* grad_inputs, void* stream);
+
 /* Backward of epropnp_shift_poses w.r.t. the pose (the offset is a constant, pnp_normalize detaches it):
  * grad_out (P,B,pose_len) -> grad_pose (P,B,pose_len). */
 int epropnp_shift_poses_backward(const float* pose, const float* offset, const float* grad_out, int32_t num_poses,
