@@ -1,5 +1,5 @@
-// amis_common.h -- pieces of the AMIS sampler shared by the two forward kernels (VALU sweep / MFMA sweep):
-// proposal fitting, proposal densities, sampling, weight algebra.  See amis_kernels.hip for the reference map.
+// amis_common.h -- the stages of the AMIS sampler around the forward kernel's cost sweep (amis_forward_mfma.hip):
+// proposal fitting, proposal densities, sampling, weight algebra.  See amis_forward_mfma.hip for the reference map.
 #pragma once
 #include "pnp_host.h"
 #include "tuning.h"
@@ -58,12 +58,11 @@ constexpr int kPropStride = 40;   // floats per fitted proposal (layout below)
 //   [37] 1 if the translation covariance fell back to its default factor, [38] 1 if the ACG shape matrix did
 //   (cholesky_wrapper, epropnp.py:16-33) -- reported through the status word as EPROPNP_ST_CHOL_FALLBACK
 constexpr int kVmTries = PNP_VM_TRIES;             // (tuning.h; the injected-noise layout assumes 16)
-constexpr int kRedStride = 68;                      // 64 lanes + 4 floats of padding per parked sample
-constexpr int kWaveRed = 16 * kRedStride + 64;     // per-wave LDS scratch of the transposed cost reduction
 
 struct AmisParams {
   int S, K;            // total samples, iterations
-  int WP;              // waves that split the points (W = WS * WP)
+  int unused_wp;       // read by nobody (always 1).  The slot stays: without it the kernel arguments shift and the forward's SGPR
+                       // spills move with them -- a change to the hot kernel that wants a measurement of its own
   float eps;
   int mle_iter;
   float dispersion;
@@ -189,15 +188,10 @@ PNP_FN void wave_sum_t(float (&v)[NV], float* lds, int lane) {
   wave_lds_fence();
 }
 
-// the refit's cross-lane sums: transposed through `scratch`, or (no scratch: the all-VALU forward kernel) wave_sum chains
+// the refit's cross-lane sums: transposed through `scratch`
 template <int NV, int ROWS = kRefitMaxVals>
 PNP_FN void refit_sum(float (&v)[NV], float* scratch, int lane) {
-  if (scratch != nullptr) {
-    wave_sum_t<NV, ROWS>(v, scratch, lane);
-  } else {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
-  }
+  wave_sum_t<NV, ROWS>(v, scratch, lane);
 }
 
 // Translation (3x3) and rotation (4x4, ACG) factors of a proposal fitted by TWO lanes in lockstep: lane 0 takes the rotation
@@ -491,7 +485,7 @@ struct AmisCtx {
   float* prop;    // [K][kPropStride] fitted proposals
   float* red;     // [256]        block-reduction scratch
   float* nzb;     // [s][8] base noise of the NEXT draw, generated ahead by the idle waves (nullptr: drawn inline)
-  float* rred;    // [kRefitRedFloats] scratch of the refit's single-wave transposed reductions (nullptr: DPP / readlane chains)
+  float* rred;    // [kRefitRedFloats] scratch of the refit's single-wave transposed reductions
   int S, K, s, T, tid, b;
   int cstride;    // row stride of cpart (s, or s rounded up to 16 for the MFMA kernel)
 };

@@ -1,7 +1,15 @@
-// amis_forward_mfma.hip -- AMIS forward with the pose x point projection on the matrix cores.
+// amis_forward_mfma.hip -- the AMIS Monte-Carlo pose sampler (forward) for gfx950, with the pose x point projection on the
+// matrix cores: the one forward kernel and its launcher.
 //
-// Same algorithm and LDS-resident sampler state as amis_forward_kernel (amis_kernels.hip); only the cost sweep
-// differs.  The projection h = (K R | K t) (X,Y,Z,1)^T of 16 poses x 16 points is ONE matrix instruction per image row
+// Replaces the loop of EProPnPBase.monte_carlo_forward (epropnp/epropnp.py:132-182) with ONE kernel:
+// initial_fit (:216-220,:288-302), sampling from Student-t x {ACG | von-Mises/uniform mix}
+// (pyro MultivariateStudentT, epropnp/distributions.py:42-72), the cost sweep over s poses x N points (:151),
+// proposal log-densities and the mixture weight algebra (:156-169), and estimate_params (:238-260,:317-342).
+// The reference materialises (s,B,N,3) broadcasts and keeps them for autograd (~12 MB per object); here one
+// workgroup owns one object (or a part of one) and the sampler state lives in LDS ("lane = sample" outside the sweep;
+// the stages are in amis_common.h).
+//
+// The projection h = (K R | K t) (X,Y,Z,1)^T of 16 poses x 16 points is ONE matrix instruction per image row
 // (x, y, z):
 //   * register mode (an object's points resident in the waves' registers: the default up to 2048 points per part), BF16:
 //     v_mfma_f32_16x16x32_bf16 on operands split into three bf16 pieces each (wave_ops.h: ProjOp<true>; fp32-level accuracy,
@@ -489,7 +497,7 @@ struct FwdPlan {
 
 constexpr size_t kLdsPerCu = 160 * 1024, kLdsGranule = 1280;      // gfx950: LDS is handed out in blocks of 320 dwords
 
-// Which instantiation launch_amis_forward_mfma launches for a problem, and with what shape: a pure host function of the sizes,
+// Which instantiation launch_amis_forward launches for a problem, and with what shape: a pure host function of the sizes,
 // the tuning variables and the CU count (launches nothing, reads no device memory).  The launcher below calls it, and so does
 // epropnp_plan_amis_forward (c_api.hip) -- the tests' way of asserting WHICH kernel a case runs -- so the two cannot drift.
 // `scratch_bytes`: what the caller's split scratch holds (0: none).
@@ -629,9 +637,16 @@ int plan_amis_forward_record(const epropnp_problem* prob, int S, int K, unsigned
   return EPROPNP_OK;
 }
 
-int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_params* am, const float* pose_opt,
-                             const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
-                             float* proposals, hipStream_t st, const DenormOut* dn, float* sample_costs) {
+int launch_amis_forward(const epropnp_problem* prob, const epropnp_amis_params* am, const float* pose_opt,
+                        const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
+                        float* proposals, hipStream_t st, const DenormOut* dn, float* sample_costs) {
+  if (int rc = check_problem(prob)) return rc;
+  if (!am) return fail(EPROPNP_EINVAL, "amis_forward: params NULL");
+  if (am->num_iter <= 0 || am->mc_samples <= 0 || am->mc_samples % am->num_iter != 0)
+    return fail(EPROPNP_EINVAL, "amis_forward: mc_samples (%d) must be a positive multiple of num_iter (%d)",
+                am->mc_samples, am->num_iter);
+  if (prob->num_obj == 0) return EPROPNP_OK;
+  if (!pose_opt || !pose_cov || !pose_samples || !logweights) return fail(EPROPNP_EINVAL, "amis_forward: NULL pointer");
   const Problem d = to_device_problem(prob);
   const int S = am->mc_samples, K = am->num_iter;
   const int PL = prob->dof == 6 ? 7 : 4;
@@ -642,7 +657,7 @@ int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_par
   const size_t smem = plan.smem;
   const bool bf16 = plan.bf16;
   AmisParams k;
-  k.S = S; k.K = K; k.WP = 1; k.eps = am->eps; k.mle_iter = am->acg_mle_iter; k.dispersion = am->acg_dispersion;
+  k.S = S; k.K = K; k.unused_wp = 1; k.eps = am->eps; k.mle_iter = am->acg_mle_iter; k.dispersion = am->acg_dispersion;
   k.seed = am->seed; k.offset = am->offset; k.offset_dev = (const unsigned long long*)am->offset_dev; k.ablate = 0;
   k.advance = (am->advance && am->advance_ticket && am->advance_count > 0) ? (unsigned long long*)am->advance : nullptr;
   k.advance_ticket = (int*)am->advance_ticket; k.advance_count = am->advance_count;

@@ -1,17 +1,10 @@
-// amis_kernels.hip -- the AMIS Monte-Carlo pose sampler (forward) and its gradient (backward) for gfx950: the all-VALU
-// kernels plus the two launchers.  The default paths are the matrix-core variants (amis_forward_mfma.hip,
-// amis_backward_mfma.hip), which share the sampler stages of amis_common.h; the kernels in this file are selected with
-// EPROPNP_{FWD,BWD}_IMPL=valu and take over where the MFMA backward's LDS pose table does not fit (> ~2700 samples).
+// amis_kernels.hip -- the all-VALU gradient (backward) of the AMIS Monte-Carlo pose sampler for gfx950, the Huber threshold's
+// follow-up launch (delta_path_kernel) and the backward launchers.  The default backward is the matrix-core variant
+// (amis_backward_mfma.hip); the kernel in this file is selected with EPROPNP_TUNE="bwd_impl=valu" and takes over where the MFMA
+// backward's LDS pose table does not fit (> ~2700 samples).  The forward has one implementation, kernel and launcher, in
+// amis_forward_mfma.hip.
 //
-// Forward replaces the loop of EProPnPBase.monte_carlo_forward (epropnp/epropnp.py:132-182) with ONE kernel:
-// initial_fit (:216-220,:288-302), sampling from Student-t x {ACG | von-Mises/uniform mix}
-// (pyro MultivariateStudentT, epropnp/distributions.py:42-72), the cost sweep over s poses x N points (:151),
-// proposal log-densities and the mixture weight algebra (:156-169), and estimate_params (:238-260,:317-342).
-// The reference materialises (s,B,N,3) broadcasts and keeps them for autograd (~12 MB per object); here one
-// workgroup owns one object, its points sit in registers ("lane = point" during the sweep), samples live in LDS
-// ("lane = sample" for everything else) and the two views are bridged with v_readlane broadcasts.
-//
-// Backward replaces autograd's replay of the same sweep: gradients of
+// Backward replaces autograd's replay of the forward's cost sweep: gradients of
 //   sum_j g_logw[j] * (-cost(pose_j)) + g_init * cost(pose_init)
 // w.r.t. x3d, x2d, w2d, delta are RECOMPUTED from the points (lane = point, loop over poses; no atomics,
 // nothing saved by the forward except the pose samples themselves).
@@ -20,133 +13,6 @@
 
 namespace pnp {
 
-// ================================================================================================================
-// forward
-// ================================================================================================================
-template <int DOF, int PPL, bool BOUNDS, int MAXW>
-__global__ __launch_bounds__(MAXW * 64, (MAXW == 4 ? (PPL >= 8 ? 2 : 3) : 1)) void amis_forward_kernel(Problem p, AmisParams a_in,
-                                                                   const float* __restrict__ pose_opt,
-                                                                   const float* __restrict__ pose_cov,
-                                                                   const float* __restrict__ noise,
-                                                                   float* __restrict__ pose_samples,
-                                                                   float* __restrict__ logweights,
-                                                                   float* __restrict__ proposals) {
-  constexpr int PL = PoseLen<DOF>::value;
-  constexpr int NZ = (DOF == 6) ? 8 : 4 + 3 * kVmTries;
-  const int b = object_of_block(p.B);
-  if (b >= p.B) return;
-  AmisParams a = a_in;
-  if (a.offset_dev != nullptr) a.offset += *a.offset_dev;
-  const int T = (int)blockDim.x, tid = (int)threadIdx.x, lane = lane_id(), wv = wave_id();
-  const int S = a.S, K = a.K, s = S / K, WP = a.WP, WS = (T >> 6) / WP;
-  const int wp = wv % WP, ws = wv / WP;
-
-  PNP_DYN_SMEM(float, smem);
-  float* ptab = smem;                 // [s][12] K R | K t of the current iteration's samples (16-B aligned rows)
-  float* wred = ptab + 12 * s;        // [waves][kWaveRed] transposed cost reduction (float4 views: 16-B aligned)
-  float* smp = wred + (T >> 6) * kWaveRed;   // [PL][S]
-  float* cst = smp + PL * S;          // [S]   cost of each sample
-  float* mixl = cst + S;              // [S]   log sum_j q_j(sample)
-  float* lgw = mixl + S;              // [S]   log weight
-  float* cpart = lgw + S;             // [WP][s] partial costs of the current iteration
-  float* prop = cpart + WP * s;       // [K][kPropStride]
-  float* red = prop + K * kPropStride;   // [16*16] reduction scratch
-
-  float Kc[9], delta;
-  Bounds bd;
-  load_camera<BOUNDS>(p, b, Kc, bd, delta);
-  // this wave's slice of the points: lane = point; kept in the pre-multiplied form the sweep consumes
-  SweepPoint pts[PPL];
-#pragma unroll
-  for (int k = 0; k < PPL; ++k) pts[k] = to_sweep_point(load_point(p, b, wp * 64 + lane + k * 64 * WP));
-  // wave-uniform operands of the sweep live in VGPRs: an SGPR source halves the VALU issue rate on gfx950
-  // (profiles/r01_ubench_valu_rates.txt: v_fma_f32 1.05 ns vs 1.84 ns per wave-instruction with an SGPR operand)
-  const float zmin_v = to_vgpr(p.z_min), delta_v = to_vgpr(delta);
-
-  if (tid < (DOF == 6 ? 2 : 1))
-    initial_fit<DOF>(pose_opt + (size_t)b * PL, pose_cov + (size_t)b * DOF * DOF, a.eps, a.dispersion, prop, tid);
-  if (tid == (int)blockDim.x - 1) denormalise_pose_opt<DOF>(a, pose_opt, b);
-  __syncthreads();
-
-  AmisCtx cx;
-  cx.ptab = ptab; cx.smp = smp; cx.cst = cst; cx.mixl = mixl; cx.lgw = lgw; cx.cpart = cpart; cx.prop = prop; cx.red = red;
-  cx.S = S; cx.K = K; cx.s = s; cx.T = T; cx.tid = tid; cx.b = b; cx.cstride = s;
-  cx.nzb = nullptr;
-  cx.rred = nullptr;      // (this kernel's LDS budget is its sample table: the refit sums stay on DPP / readlane chains)
-
-  for (int it = 0; it < K; ++it) {
-    amis_draw<DOF>(cx, p, a, it, Kc, noise, pose_samples);
-    __syncthreads();
-
-    // ---------------- 2. cost sweep: s poses x this wave's points (lane = point) ----------------
-    const int ntile = (s + 63) >> 6;
-    if (PNP_ABLATED(a, 1)) {
-      for (int n = tid; n < s; n += T) cpart[n] = 1.0f;
-    } else
-    for (int t = ws; t < ntile; t += WS) {
-      const int base = t * 64;
-      const int cnt = min(64, s - base);
-      float mine = 0.f;
-      // Per-lane partial costs of 16 samples are parked in LDS (one ds_write each, no dependent chain in the hot
-      // loop) and summed "transposed": lane l adds the 16 partials of sample (l & 15) held by lanes 16q..16q+15
-      // (q = l >> 4), then the four quarter sums are combined through a second 64-float exchange.
-      float* rt = wred + wv * kWaveRed;
-      float* rq = rt + 16 * kRedStride;
-      for (int j0 = 0; j0 < cnt; j0 += 16) {
-        const int g = min(16, cnt - j0);
-        for (int jj = 0; jj < g; ++jj) {
-          const float4* row = reinterpret_cast<const float4*>(ptab + 12 * (base + j0 + jj));   // uniform: LDS broadcast
-          const float4 r0 = row[0], r1 = row[1], r2 = row[2];
-          const float kr[9] = {r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r2.x, r2.y, r2.z};
-          const float kt[3] = {r0.w, r1.w, r2.w};
-          float c = 0.f;
-#pragma unroll
-          for (int k = 0; k < PPL; ++k) c += sweep_cost<BOUNDS>(pts[k], kr, kt, zmin_v, delta_v, bd);
-          rt[jj * kRedStride + lane] = c;
-        }
-        wave_lds_fence();
-        const float4* col = reinterpret_cast<const float4*>(rt + (lane & 15) * kRedStride + 16 * (lane >> 4));
-        const float4 v0 = col[0], v1 = col[1], v2 = col[2], v3 = col[3];
-        const float quarter = ((v0.x + v0.y) + (v0.z + v0.w)) + ((v1.x + v1.y) + (v1.z + v1.w)) +
-                              (((v2.x + v2.y) + (v2.z + v2.w)) + ((v3.x + v3.y) + (v3.z + v3.w)));
-        rq[(lane & 15) * 4 + (lane >> 4)] = quarter;
-        wave_lds_fence();
-        const float4 q4 = *reinterpret_cast<const float4*>(rq + (lane & 15) * 4);
-        const float total = (q4.x + q4.y) + (q4.z + q4.w);
-        mine = ((lane >> 4) == (j0 >> 4)) ? total : mine;   // lanes j0..j0+15 own samples j0..j0+15 of the tile
-        wave_lds_fence();                                   // rt / rq are rewritten by the next group
-      }
-      if (base + lane < s) cpart[wp * s + base + lane] = mine;
-    }
-    __syncthreads();
-
-    amis_weights<DOF>(cx, a, it, WP);
-    __syncthreads();
-    if (it == K - 1) break;
-    amis_refit<DOF>(cx, a, it);
-  }
-
-  // ---------------- outputs ----------------
-  {   // numerical events for the caller's status word (include/epropnp_hip.h); no-op without one
-    int st_bits = 0;
-    for (int m = tid; m < S; m += T) {
-      const float lw = lgw[m];
-      logweights[(size_t)m * p.B + b] = lw;
-      if (a.sample_costs != nullptr) a.sample_costs[(size_t)m * p.B + b] = cst[m];
-      st_bits |= (lw == lw && lw != INFINITY) ? 0 : EPROPNP_ST_NONFINITE_WEIGHT;     // -inf = zero weight is legitimate
-    }
-    for (int i = tid; i < K; i += T)
-      st_bits |= (prop[i * kPropStride + 37] != 0.f || prop[i * kPropStride + 38] != 0.f) ? EPROPNP_ST_CHOL_FALLBACK : 0;
-    raise_status(p, st_bits, b);
-  }
-  if (proposals != nullptr)
-    for (int i = tid; i < K * kPropStride; i += T) proposals[(size_t)b * K * kPropStride + i] = prop[i];
-  advance_counters(a, p.B);
-}
-
-// ================================================================================================================
-// backward
-// ================================================================================================================
 template <int DOF, int PPL, bool BOUNDS, int MAXW>
 __global__ __launch_bounds__(MAXW * 64, (MAXW == 4 ? (PPL >= 8 ? 2 : (PPL == 4 ? 3 : 4)) : 1)) void amis_backward_kernel(Problem p, const float* __restrict__ pose_samples,
                                                                     const float* __restrict__ g_logw, int S,
@@ -300,69 +166,6 @@ __global__ __launch_bounds__(MAXW * 64, (MAXW == 4 ? (PPL >= 8 ? 2 : (PPL == 4 ?
 // ================================================================================================================
 // launchers
 // ================================================================================================================
-int launch_amis_forward(const epropnp_problem* prob, const epropnp_amis_params* am, const float* pose_opt,
-                        const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
-                        float* proposals, hipStream_t st, const DenormOut* dn, float* sample_costs) {
-  if (int rc = check_problem(prob)) return rc;
-  if (!am) return fail(EPROPNP_EINVAL, "amis_forward: params NULL");
-  if (am->num_iter <= 0 || am->mc_samples <= 0 || am->mc_samples % am->num_iter != 0)
-    return fail(EPROPNP_EINVAL, "amis_forward: mc_samples (%d) must be a positive multiple of num_iter (%d)",
-                am->mc_samples, am->num_iter);
-  if (prob->num_obj == 0) return EPROPNP_OK;
-  if (!pose_opt || !pose_cov || !pose_samples || !logweights) return fail(EPROPNP_EINVAL, "amis_forward: NULL pointer");
-  {   // default: projection on the matrix cores (amis_forward_mfma.hip); EPROPNP_TUNE="fwd_impl=valu" keeps the VALU sweep
-    const char* impl = tune_value("fwd_impl");
-    if (!(impl && impl[0] == 'v'))
-      return launch_amis_forward_mfma(prob, am, pose_opt, pose_cov, noise, pose_samples, logweights, proposals, st, dn, sample_costs);
-  }
-  if (prob->num_pts > kMaxResidentPoints)
-    return fail(EPROPNP_EINVAL, "amis_forward: num_pts %d exceeds the register-resident limit %d", prob->num_pts,
-                kMaxResidentPoints);
-  const Problem d = to_device_problem(prob);
-  const int S = am->mc_samples, K = am->num_iter, s = S / K;
-  const int PL = prob->dof == 6 ? 7 : 4;
-  // shape: WP waves split the points (as few as possible: <= 8 points per lane), WS waves split the sample tiles
-  int WP = 1;
-  while (64 * WP * 8 < d.N && WP < 16) WP *= 2;
-  int ppl = 1;
-  while (64 * WP * ppl < d.N) ppl *= 2;
-  const int ntile = (s + 63) / 64;
-  int WS = 1;
-  while (WS * 2 <= ntile && WS * 2 * WP <= 8) WS *= 2;
-  // few objects: trade points-per-lane for more point-waves to fill the machine (<= 8 waves: no register spills)
-  while ((long)d.B * WS * WP < 2048 && ppl > 1 && WS * WP * 2 <= 8) {
-    WP *= 2;
-    ppl /= 2;
-  }
-  int ov[3];   // WS, WP, PPL
-  if (tune_ints("fwd_shape", ov, 3) && valid_shape_override(ov[1], ov[2], d.N) && ov[0] >= 1 && ov[0] * ov[1] <= 16 &&
-      (ov[0] & (ov[0] - 1)) == 0) {
-    WS = ov[0]; WP = ov[1]; ppl = ov[2];
-  }
-  AmisParams k;
-  k.split_timeout = 0;
-  k.S = S; k.K = K; k.WP = WP; k.eps = am->eps; k.mle_iter = am->acg_mle_iter; k.dispersion = am->acg_dispersion;
-  k.seed = am->seed; k.offset = am->offset; k.offset_dev = (const unsigned long long*)am->offset_dev;
-  k.advance = (am->advance && am->advance_ticket && am->advance_count > 0) ? (unsigned long long*)am->advance : nullptr;
-  k.advance_ticket = (int*)am->advance_ticket; k.advance_count = am->advance_count;
-  k.ablate = 0;
-  k.dn_offset = dn ? dn->offset : nullptr; k.dn_samples = dn ? dn->samples : nullptr; k.dn_pose_opt = dn ? dn->pose_opt : nullptr;
-  k.sample_costs = sample_costs;
-  { int ab[1]; if (tune_ints("ablate", ab, 1)) k.ablate = ab[0]; }
-  // the float4-viewed arrays (ptab rows, wred) come first so that they are 16-B aligned for any S
-  const size_t smem = sizeof(float) * (12 * (size_t)s + (size_t)PL * S + 3 * (size_t)S + (size_t)WP * s +
-                                       (size_t)K * kPropStride + 256 + (size_t)WS * WP * kWaveRed);
-  if (smem > 160 * 1024) return fail(EPROPNP_EINVAL, "amis_forward: mc_samples %d needs %zu B of LDS (> 160 KiB)", S, smem);
-  const dim3 grid(padded_object_grid(d.B)), block(64 * WS * WP);
-  dispatch_shape(prob->dof, ppl, has_bounds(prob), WS * WP, [&](auto DOF, auto PPL, auto BND, auto MAXW) -> int {
-    auto kern = amis_forward_kernel<decltype(DOF)::value, decltype(PPL)::value, decltype(BND)::value, decltype(MAXW)::value>;
-    allow_dynamic_lds((const void*)kern, smem);
-    PNP_LAUNCH(kern, grid, block, smem, st, d, k, pose_opt, pose_cov, noise, pose_samples, logweights, proposals);
-    return 0;
-  });
-  return check_launch("amis_forward_kernel");
-}
-
 // grad_w2d[b, :, :] += (sum over parts of grad_delta[b, part]) * d delta[b] / d w2d  for a Huber threshold that came from
 // AdaptiveHuberPnPCost on this w2d (epropnp_problem.delta_stats): the follow-up launch for the backward variants whose kernel
 // does not know the object's whole grad_delta at its end (object split over workgroups; the all-VALU kernel).

@@ -351,9 +351,6 @@ struct DenormOut { const float* offset; float* samples; float* pose_opt; };
 int launch_amis_forward(const epropnp_problem* prob, const epropnp_amis_params* amis, const float* pose_opt,
                         const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
                         float* proposals, hipStream_t st, const DenormOut* dn = nullptr, float* sample_costs = nullptr);
-int launch_amis_forward_mfma(const epropnp_problem* prob, const epropnp_amis_params* amis, const float* pose_opt,
-                             const float* pose_cov, const float* noise, float* pose_samples, float* logweights,
-                             float* proposals, hipStream_t st, const DenormOut* dn = nullptr, float* sample_costs = nullptr);
 int launch_amis_backward_split(const epropnp_problem* prob, const float* pose_samples, const float* grad_logweights,
                                int mc_samples, const float* pose_init, const float* grad_cost_init, int nsplit,
                                float* grad_x3d, float* grad_x2d, float* grad_w2d, float* grad_delta_parts, hipStream_t st,

@@ -2,7 +2,7 @@
 
 API mirror of the reference's epropnp/distributions.py (AngularCentralGaussian :15-52, VonMisesUniformMix :55-79),
 kept for callers that build these objects directly (visualisation / diagnostics).  The sampler itself evaluates the
-same densities inside the HIP kernel (csrc/amis_kernels.hip); it does not construct these classes.
+same densities inside the HIP kernel (csrc/amis_common.h); it does not construct these classes.
 Unlike the reference there is no pyro dependency (its base class is torch's own Distribution) and the von Mises
 draw stays on the tensor's device (torch's sampler) instead of round-tripping through numpy on the host.
 """

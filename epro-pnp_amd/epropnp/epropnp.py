@@ -3,8 +3,8 @@
 API mirror of the reference's epropnp/epropnp.py (EProPnPBase :36-196, EProPnP4DoF :199-260, EProPnP6DoF :263-342):
 same constructor arguments, `forward` / `monte_carlo_forward` signatures and 6-tuple return.  Where the reference
 runs a Python loop of ~150 ATen launches per AMIS iteration with host round-trips for every Cholesky, this layer
-makes three HIP launches in total: cost of pose_init, the fused LM solve, and the fused AMIS sampler; the backward
-is one more launch that recomputes the cost sweep (csrc/amis_kernels.hip).
+makes three HIP launches in total: cost of pose_init, the fused LM solve, and the fused AMIS sampler
+(csrc/amis_forward_mfma.hip); the backward is one more launch that recomputes the cost sweep (csrc/amis_backward_mfma.hip).
 
 Extra (non-reference) knobs, all optional:
   * `seed`            : Philox key of the on-device sampler (default: drawn once from torch's global generator)

@@ -84,6 +84,24 @@ def _mixture_logq(samples, props, dof, K):
     return torch.logsumexp(torch.stack(lq, 0), 0) - torch.log(torch.tensor(float(K)))
 
 
+def _ocam64(prob):
+    return orc.Cam(prob['cam_mats'].double(), 0.1, *(prob[k].double() if k in prob else None for k in ('lb', 'ub')))
+
+
+def _check_logweights(prob, dof, K, samples, logw, props):
+    """log-weights against the fp64 oracle's cost plus the mixture density at the kernel's own samples and proposals"""
+    samples, logw, props = samples.cpu(), logw.cpu(), props.cpu()
+    assert bool(torch.isfinite(samples).all()) and bool(torch.isfinite(props).all())
+    cost = orc.evaluate(prob['x3d'].double(), prob['x2d'].double(), prob['w2d'].double(), samples.double(), _ocam64(prob),
+                        prob['delta'].double(), want_cost=True)[1]
+    expect = -cost.float() - _mixture_logq(samples, props, dof, K)
+    fin = torch.isfinite(expect)
+    assert bool((torch.isfinite(logw) == fin).all())
+    err, scale = (logw[fin] - expect[fin]).abs().max().item(), max(1.0, expect[fin].abs().max().item())
+    print(f'logw err {err:.3e} (bar {2e-4 * scale:.3e})')
+    assert err <= 2e-4 * scale
+
+
 @pytest.mark.parametrize('dof,S,K,N', [(6, 64, 4, 96), (4, 64, 4, 96), (6, 60, 3, 70), (6, 200, 2, 130), (4, 100, 1, 33),
                                        (6, 320, 2, 600), (6, 48, 2, 1300), (6, 32, 2, 2300), (6, 32, 2, 512), (4, 32, 2, 2040),
                                        (6, 32, 2, 800), (6, 40, 2, 2048),
@@ -416,7 +434,8 @@ def test_philox_sampler_statistics(backend):
 
 
 def test_forward_kernel_variants_agree(backend, monkeypatch):
-    """EPROPNP_TUNE=fwd_impl=valu selects the register-resident VALU sweep kernel; same samples, same weights."""
+    """The forward's launch variants (EPROPNP_TUNE=fwd_mfma=.., EPROPNP_FWD_PROJ) against the default launch: same samples, same
+    weights; the default launch itself against the fp64 oracle."""
     from epropnp import functional as F
     B, N, S, K, dof = 3, 200, 64, 4, 6
     prob = orc.make_problem(B, N, dof, seed=17)
@@ -425,19 +444,22 @@ def test_forward_kernel_variants_agree(backend, monkeypatch):
     hp = F.PnPProblem(p['x3d'], p['x2d'], p['w2d'], cam, cf, dof)
     pose_opt, pose_cov, _ = F.lm_solve(hp, p['pose_init'], 3, with_pose_cov=True)
     set_tune(monkeypatch)
-    s1, w1 = F.amis_forward(hp, pose_opt, pose_cov, S, K, noise=noise)
-    set_tune(monkeypatch, fwd_impl='valu')
-    s2, w2 = F.amis_forward(hp, pose_opt, pose_cov, S, K, noise=noise)
-    assert (s1 - s2).abs().max().item() < 5e-4
-    assert (torch.logsumexp(w1, 0) - torch.logsumexp(w2, 0)).abs().max().item() < 1e-3
-    # on-device Philox draws: the MFMA kernel pre-generates the base noise into LDS shared with its pose table, the VALU
-    # kernel draws inline -- same counters, same samples
-    set_tune(monkeypatch)
+    s1, w1, pr1 = F.amis_forward(hp, pose_opt, pose_cov, S, K, noise=noise, with_proposals=True)
+    _check_logweights(prob, dof, K, s1, w1, pr1)
+    # on-device Philox draws: the multi-wave kernel pre-generates the base noise into LDS shared with its pose table, a one-wave
+    # launch draws inline (LDS-streamed and register mode) -- same counters, same samples
     p1, q1 = F.amis_forward(hp, pose_opt, pose_cov, S, K, seed=42, offset=7)
-    set_tune(monkeypatch, fwd_impl='valu')
-    p2, q2 = F.amis_forward(hp, pose_opt, pose_cov, S, K, seed=42, offset=7)
-    assert (p1 - p2).abs().max().item() < 5e-4
-    assert (torch.logsumexp(q1, 0) - torch.logsumexp(q2, 0)).abs().max().item() < 1e-3
+    s = S // K
+    for shape in ('1,0', '1,16'):
+        set_tune(monkeypatch, fwd_mfma=shape)
+        plan = F.launch_plan('forward', hp, S, K)
+        assert plan['waves'] == 1 and plan['G'] == 1 and plan['tiles'] == int(shape[2:]), plan
+        p2, q2 = F.amis_forward(hp, pose_opt, pose_cov, S, K, seed=42, offset=7)
+        assert torch.equal(p1[:s], p2[:s])                          # the first iteration's samples do not depend on the sweep
+        print(f'fwd_mfma={shape}: samples {(p1 - p2).abs().max().item():.3e}, '
+              f'logsumexp {(torch.logsumexp(q1, 0) - torch.logsumexp(q2, 0)).abs().max().item():.3e}')
+        assert (p1 - p2).abs().max().item() < 5e-4
+        assert (torch.logsumexp(q1, 0) - torch.logsumexp(q2, 0)).abs().max().item() < 1e-3
     # MFMA kernel, LDS-chunk mode (used for N > 2048), forced on this small problem with 2 waves
     set_tune(monkeypatch)
     set_tune(monkeypatch, fwd_mfma='2,0')
@@ -450,7 +472,6 @@ def test_forward_kernel_variants_agree(backend, monkeypatch):
     monkeypatch.setenv('EPROPNP_FWD_PROJ', 'f32')
     s4, w4 = F.amis_forward(hp, pose_opt, pose_cov, S, K, noise=noise)
     monkeypatch.delenv('EPROPNP_FWD_PROJ')
-    s = S // K
     assert torch.equal(s1[:s], s4[:s])
     assert not torch.equal(w1, w4)                                  # (the switch does select another kernel)
     assert (s1 - s4).abs().max().item() < 5e-4

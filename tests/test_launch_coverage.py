@@ -14,7 +14,7 @@ import torch
 
 import epropnp_oracle as orc
 from helpers import make_layer_objects, pack_noise, set_tune
-from test_amis import GRAD_TOL, _mixture_logq, _rel  # noqa: F401  (_rel: the yardstick the bars were written in)
+from test_amis import GRAD_TOL, _check_logweights, _mixture_logq, _ocam64, _rel  # noqa: F401  (_rel: the yardstick the bars were written in)
 
 SK = [(32, 2), (80, 2)]      # S = 80, K = 2: 40 samples per iteration, a pose tile padded from 40 to 48 rows
 
@@ -31,10 +31,6 @@ def _setup(dev, B, N, dof, bounds, seed):
     return prob, p, F.PnPProblem(p['x3d'], p['x2d'], p['w2d'], cam, cf, dof)
 
 
-def _ocam64(prob):
-    return orc.Cam(prob['cam_mats'].double(), 0.1, *(prob[k].double() if k in prob else None for k in ('lb', 'ub')))
-
-
 def _take(prob, idx):
     """the objects `idx` of a problem dict as a problem of their own"""
     return {k: (v[idx].contiguous() if isinstance(v, torch.Tensor) and v.dim() > 0 else v) for k, v in prob.items()}
@@ -43,20 +39,6 @@ def _take(prob, idx):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # forward
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _check_logweights(prob, dof, K, samples, logw, props):
-    """log-weights against the fp64 oracle's cost plus the mixture density at the kernel's own samples and proposals"""
-    samples, logw, props = samples.cpu(), logw.cpu(), props.cpu()
-    assert bool(torch.isfinite(samples).all()) and bool(torch.isfinite(props).all())
-    cost = orc.evaluate(prob['x3d'].double(), prob['x2d'].double(), prob['w2d'].double(), samples.double(), _ocam64(prob),
-                        prob['delta'].double(), want_cost=True)[1]
-    expect = -cost.float() - _mixture_logq(samples, props, dof, K)
-    fin = torch.isfinite(expect)
-    assert bool((torch.isfinite(logw) == fin).all())
-    err, scale = (logw[fin] - expect[fin]).abs().max().item(), max(1.0, expect[fin].abs().max().item())
-    print(f'logw err {err:.3e} (bar {2e-4 * scale:.3e})')
-    assert err <= 2e-4 * scale
-
-
 def _forward(dev, hp, prob, dof, S, K, noise=None, lm=None):
     from epropnp import functional as F
     if noise is None:
