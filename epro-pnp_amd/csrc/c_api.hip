@@ -313,6 +313,28 @@ int epropnp_roi_logsumexp_backward(const float* roi_inputs, const float* rois, c
                                             (hipStream_t)stream);
 }
 
+int epropnp_roi_align_forward(const float* map0, const float* map1, const float* rois, int32_t num_rois, int32_t num_img,
+                              int32_t channels, int32_t height, int32_t width, int32_t out_height, int32_t out_width,
+                              float spatial_scale, int32_t sampling_ratio, int32_t aligned, int64_t map_stride_n, int64_t map_stride_c,
+                              int64_t map_stride_h, int64_t map_stride_w, int64_t out_stride_n, int64_t out_stride_c,
+                              int64_t out_stride_h, int64_t out_stride_w, float* out0, float* out1, void* stream) {
+  pnp::StageScope prof_("roi_align_forward", (hipStream_t)stream);
+  return pnp::launch_roi_align_forward(map0, map1, rois, num_rois, num_img, channels, height, width, out_height, out_width, spatial_scale,
+                                       sampling_ratio, aligned, map_stride_n, map_stride_c, map_stride_h, map_stride_w, out_stride_n,
+                                       out_stride_c, out_stride_h, out_stride_w, out0, out1, (hipStream_t)stream);
+}
+
+int epropnp_roi_align_backward(const float* grad_out0, const float* grad_out1, const float* rois, int32_t num_rois, int32_t num_img,
+                               int32_t channels, int32_t height, int32_t width, int32_t out_height, int32_t out_width,
+                               float spatial_scale, int32_t sampling_ratio, int32_t aligned, int64_t map_stride_n, int64_t map_stride_c,
+                               int64_t map_stride_h, int64_t map_stride_w, int64_t out_stride_n, int64_t out_stride_c,
+                               int64_t out_stride_h, int64_t out_stride_w, float* grad_map0, float* grad_map1, void* stream) {
+  pnp::StageScope prof_("roi_align_backward", (hipStream_t)stream);
+  return pnp::launch_roi_align_backward(grad_out0, grad_out1, rois, num_rois, num_img, channels, height, width, out_height, out_width,
+                                        spatial_scale, sampling_ratio, aligned, map_stride_n, map_stride_c, map_stride_h, map_stride_w,
+                                        out_stride_n, out_stride_c, out_stride_h, out_stride_w, grad_map0, grad_map1, (hipStream_t)stream);
+}
+
 int epropnp_evaluate_cost(const epropnp_problem* prob, const float* poses, int32_t num_poses, float* cost, void* stream) {
   pnp::StageScope prof_("evaluate_cost", (hipStream_t)stream);
   return pnp::launch_evaluate_cost(prob, poses, num_poses, cost, (hipStream_t)stream);

@@ -318,6 +318,14 @@ int launch_deform_backward(const float* query, const float* key, const float* va
 int launch_roi_logsumexp_forward(const float* x, const float* rois, int n, int c, int rh, int rw, float* out, hipStream_t st);
 int launch_roi_logsumexp_backward(const float* x, const float* rois, const float* out, const float* gout, int n, int c, int rh, int rw,
                                   float* gx, hipStream_t st);
+// roi_align_kernels.hip: RoIAlign ('avg') of one or two maps of identical geometry (epropnp_roi_align_forward / _backward): one launch
+// each; the backward gathers by destination and writes every element of the gradient maps once -- no zero fill, no atomics
+int launch_roi_align_forward(const float* map0, const float* map1, const float* rois, int bn, int NI, int C, int h, int w, int ph, int pw,
+                             float scale, int sampling, int aligned, long long sN, long long sC, long long sH, long long sW,
+                             long long oN, long long oC, long long oH, long long oW, float* out0, float* out1, hipStream_t st);
+int launch_roi_align_backward(const float* gout0, const float* gout1, const float* rois, int bn, int NI, int C, int h, int w, int ph,
+                              int pw, float scale, int sampling, int aligned, long long sN, long long sC, long long sH, long long sW,
+                              long long oN, long long oC, long long oH, long long oW, float* gmap0, float* gmap1, hipStream_t st);
 // grad_w2d += grad_delta * d delta / d w2d for a threshold from AdaptiveHuberPnPCost (epropnp_problem.delta_stats); no-op without
 int launch_delta_path(const epropnp_problem* prob, const float* gdelta, int nparts, float* gw2d, hipStream_t st);
 // stream-ordered fill as a kernel (never hipMemsetAsync: eval_kernels.hip, fill_u32_kernel)

@@ -113,6 +113,8 @@ def _declare(lib):
     lib.epropnp_deform_sample_backward.argtypes = [vp] * 13 + [i32] * 8 + [i64] * 4 + [vp] * 5
     lib.epropnp_roi_logsumexp_forward.argtypes = [vp] * 2 + [i32] * 4 + [vp] * 2
     lib.epropnp_roi_logsumexp_backward.argtypes = [vp] * 4 + [i32] * 4 + [vp] * 2
+    lib.epropnp_roi_align_forward.argtypes = [vp] * 3 + [i32] * 7 + [f32] + [i32] * 2 + [i64] * 8 + [vp] * 3
+    lib.epropnp_roi_align_backward.argtypes = [vp] * 3 + [i32] * 7 + [f32] + [i32] * 2 + [i64] * 8 + [vp] * 3
     lib.epropnp_evaluate_cost.argtypes = [C.POINTER(Problem), vp, i32, vp, vp]
     lib.epropnp_normal_equations.argtypes = [C.POINTER(Problem), vp, i32, vp, vp, vp, vp]
     lib.epropnp_cost_pose_cam_grad.argtypes = [C.POINTER(Problem), vp, vp, i32, i32, vp, vp, vp]
@@ -161,7 +163,7 @@ def _declare(lib):
                  'posterior_modes', 'amis_forward_costs', 'monte_carlo_forward_costs', 'amis_backward_costs',
                  'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms', 'orient_density',
                  'bev_density', 'deform_sample_forward', 'deform_sample_backward', 'roi_logsumexp_forward',
-                 'roi_logsumexp_backward'):
+                 'roi_logsumexp_backward', 'roi_align_forward', 'roi_align_backward'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -185,7 +187,8 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_pose_errors_scratch_bytes', 'epropnp_bev_overlap', 'epropnp_bev_nms', 'epropnp_bev_nms_scratch_bytes',
            'epropnp_orient_density', 'epropnp_orient_density_scratch_bytes', 'epropnp_bev_density',
            'epropnp_bev_density_scratch_bytes', 'epropnp_deform_sample_forward', 'epropnp_deform_sample_backward',
-           'epropnp_roi_logsumexp_forward', 'epropnp_roi_logsumexp_backward')
+           'epropnp_roi_logsumexp_forward', 'epropnp_roi_logsumexp_backward', 'epropnp_roi_align_forward',
+           'epropnp_roi_align_backward')
 
 
 def lib():

@@ -736,6 +736,39 @@ int epropnp_roi_logsumexp_forward(const float* roi_inputs, const float* rois, in
 int epropnp_roi_logsumexp_backward(const float* roi_inputs, const float* rois, const float* out, const float* grad_out, int32_t num_rois,
                                    int32_t channels, int32_t roi_height, int32_t roi_width, float* grad_inputs, void* stream);
 
+/* RoIAlign with average pooling, the op behind the detection head's extract_rois (EPro-PnP-Det deform_pnp_head.py:719-741, three
+ * mmcv.ops.roi_align calls through roi_align_wrapper :1187-1196), for ONE map (map1 = out1 = NULL) or TWO maps of identical shape and
+ * strides that share the per-RoI sampling tables (key and value).  map (NI,C,h,w) and out (num_rois,C,out_h,out_w) are read / written
+ * through explicit element strides (n, c, h, w): contiguous NCHW or channels-last without a copy (map_stride_c == 1 selects the
+ * channels-last kernels).  rois (num_rois,5) = [image id, x1, y1, x2, y2].  With o = 0.5 if aligned else 0:
+ *   xs = x1 scale - o, xe = x2 scale - o, rw = xe - xs (clamped to >= 1 only when not aligned), bw = rw / out_w; ys, rh, bh alike
+ *   gw = sampling_ratio if sampling_ratio > 0 else ceil(bw); gh alike; count = max(gh gw, 1)
+ *   out[r,c,i,j] = 1/count sum_{iy < gh, ix < gw} bilinear(map[n,c], y = ys + i bh + (iy + .5) bh / gh, x = xs + j bw + (ix + .5) bw / gw)
+ *   a sample with y < -1, y > h, x < -1 or x > w is 0; any other has y, x clamped to [0, h - 1], [0, w - 1]
+ * so a RoI of zero or negative size on the adaptive grid (sampling_ratio = 0) has no samples and gives zeros.  The sum is evaluated
+ * in its separable form out = Wy map Wx^T in fp64 and rounded once; every order is fixed (two launches give the same bits, and two
+ * maps give the bits of two one-map calls).  A RoI whose image id is not in [0, NI) (the id is truncated, as the reference's), whose
+ * corners are not finite or whose grid exceeds 2^30 samples per cell and axis gives zeros and no gradient: no input value forms an
+ * address unchecked.  One launch, no allocation, no synchronisation; capturable into a hipGraph.  num_rois == 0 launches nothing.
+ * EPROPNP_EINVAL: num_img / channels / height / width / out_height / out_width < 1, num_rois < 0, sampling_ratio outside 0 .. 32768,
+ * a non-finite spatial_scale, a stride below 1 or strides whose largest offset reaches outside num_img * channels * height * width
+ * (num_rois * channels * out_height * out_width) elements, a NULL pointer, map1 without out1 or the reverse. */
+int epropnp_roi_align_forward(const float* map0, const float* map1, const float* rois, int32_t num_rois, int32_t num_img,
+                              int32_t channels, int32_t height, int32_t width, int32_t out_height, int32_t out_width,
+                              float spatial_scale, int32_t sampling_ratio, int32_t aligned, int64_t map_stride_n, int64_t map_stride_c,
+                              int64_t map_stride_h, int64_t map_stride_w, int64_t out_stride_n, int64_t out_stride_c,
+                              int64_t out_stride_h, int64_t out_stride_w, float* out0, float* out1, void* stream);
+/* Its backward w.r.t. the maps (rois gets no gradient): grad_out (num_rois,C,out_h,out_w) with the out strides -> grad_map (NI,C,h,w)
+ * with the map strides, grad_map = sum_r Wy_r^T grad_out_r Wx_r, gathered by destination: every element of grad_map0 (and grad_map1)
+ * is written exactly once with a plain store, zeros included -- the buffers need no zero fill, there is no float atomic, and the RoIs
+ * are summed in ascending order: two launches give the same bits.  num_rois == 0 writes zeros.  Errors as the forward's, and
+ * num_img * ceil(channels / 64) > 65535. */
+int epropnp_roi_align_backward(const float* grad_out0, const float* grad_out1, const float* rois, int32_t num_rois, int32_t num_img,
+                               int32_t channels, int32_t height, int32_t width, int32_t out_height, int32_t out_width,
+                               float spatial_scale, int32_t sampling_ratio, int32_t aligned, int64_t map_stride_n, int64_t map_stride_c,
+                               int64_t map_stride_h, int64_t map_stride_w, int64_t out_stride_n, int64_t out_stride_c,
+                               int64_t out_stride_h, int64_t out_stride_w, float* grad_map0, float* grad_map1, void* stream);
+
 /* Backward of epropnp_shift_poses w.r.t. the pose (the offset is a constant, pnp_normalize detaches it):
  * grad_out (P,B,pose_len) -> grad_pose (P,B,pose_len). */
 int epropnp_shift_poses_backward(const float* pose, const float* offset, const float* grad_out, int32_t num_poses,
