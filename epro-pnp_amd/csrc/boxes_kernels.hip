@@ -22,6 +22,8 @@
 //       bit of a diagonal word flags a row that can never be kept (invalid box, order entry out of range).
 //   bev_nms_reduce_kernel   : one workgroup; `removed` bitset in LDS; per row tile one wave resolves the 64 diagonal words serially in
 //       registers (v_readlane), then all threads OR the kept rows' words into the later tiles' `removed` words (independent loads).
+//   box_overlap_*_kernel    : rotated, 3D and image boxes under the four criteria, pairwise / aligned / segmented, around the same
+//       bev_overlap_area (epropnp_box_overlap, epropnp_box_overlap_segmented): described where they stand, below the NMS launchers.
 // No atomics, no cross-workgroup waiting, no allocation, no synchronisation: two launches agree to the last bit.
 #include "pnp_host.h"
 
@@ -323,6 +325,253 @@ int launch_bev_nms(const float* boxes, const int32_t* order, const int32_t* grou
   PNP_LAUNCH(bev_nms_reduce_kernel, dim3(1), dim3(kBevReduceThreads), 0, st, order, N, T, (const unsigned long long*)scratch,
              keep_index, keep_mask, num_keep);
   return check_launch("bev_nms_reduce_kernel");
+}
+
+// ---- box overlaps: rotated, 3D and image boxes under the four criteria (epropnp_box_overlap, epropnp_box_overlap_segmented) ------------
+// What EPro-PnP-Det's two numba-CUDA files put around the rotated intersection (core/bbox_3d/iou_calculators/rotate_iou_kernel.py,
+// bbox3d_iou_calculator.py; core/evaluation/kitti_utils/rotate_iou.py, eval.py: image_box_overlap, d3_box_overlap_kernel).
+//   box_prepare<KIND> : a box in the form the pair routine takes.  bev: BevBox as it is.  box3d: the BevBox of the two axes that are
+//       not z_axis, and the height interval lo = z - h z_center, hi = z + h (1 - z_center).  image: (x1, y1, x2, y2) kept in the
+//       BevBox's cx, cy, hx, hy.  `size` is the area / volume / image area, `ok` the validity (all numbers finite, sizes >= 0).
+//   box_pair<KIND>    : the ONE pair function: intersection (bev_overlap_area, times the common height for box3d; iw ih for image),
+//       then the criterion; products uncontracted.  NaN exactly where either box is invalid.
+//   box_tile<KIND>    : the ONE tile body of the pairwise and the segmented kernel: up to 64 x 64 pairs, both sides' boxes prepared
+//       into LDS, a lane owns a column, a wave walks the rows.  The aligned kernel calls box_pair on its own pair: the same bits.
+//   segmented         : one workgroup per entry of a tile table built on the host (box_overlap_plan): six int32 per tile -- first row,
+//       rows (1..64), first column, columns (1..64), output index of the tile's first element, row stride of its block.  The table is
+//       memory: an entry that points outside the boxes or the output is skipped, nothing is read or written out of bounds.
+constexpr int kBoxTileInts = EPROPNP_BOX_TILE_INTS;
+
+struct OvBox {
+  BevBox b;
+  float lo, hi, size, ok;
+};
+
+struct OvMode {
+  int crit, rule, z_axis;
+  float z_center;
+};
+
+template <int KIND>
+constexpr int box_floats() { return KIND == EPROPNP_BOX_BEV ? 5 : KIND == EPROPNP_BOX_3D ? 7 : 4; }
+
+PNP_FN bool box_finite(float v) { return fabsf(v) < INFINITY; }
+
+template <int KIND>
+PNP_FN OvBox box_prepare(const float* __restrict__ p, const OvMode& m) {
+#pragma clang fp contract(off)
+  OvBox o;
+  if (KIND == EPROPNP_BOX_IMAGE) {
+    const float x1 = p[0], y1 = p[1], x2 = p[2], y2 = p[3];
+    o.b = bev_no_box();
+    o.b.cx = x1; o.b.cy = y1; o.b.hx = x2; o.b.hy = y2;
+    o.lo = o.hi = 0.f;
+    o.size = (x2 - x1) * (y2 - y1);
+    o.ok = (box_finite(x1) && box_finite(y1) && box_finite(x2) && box_finite(y2) && x2 >= x1 && y2 >= y1) ? 1.f : 0.f;
+  } else if (KIND == EPROPNP_BOX_BEV) {
+    o.b = bev_prepare(p);
+    o.lo = o.hi = 0.f;
+    o.size = o.b.area;
+    o.ok = (o.b.area == o.b.area) ? 1.f : 0.f;
+  } else {
+    // the reference's bev_axes: the seven numbers without x[z_axis] and d[z_axis] -- [0, 2, 3, 5, 6] for z_axis = 1
+    const int i0 = (m.z_axis == 0) ? 1 : 0, i1 = (m.z_axis == 2) ? 1 : 2;
+    const float q0 = p[i0], q1 = p[i1], q2 = p[3 + i0], q3 = p[3 + i1], q4 = p[6];
+    const float z = p[m.z_axis], h = p[3 + m.z_axis];
+    const float bev[5] = {q0, q1, q2, q3, q4};
+    o.b = bev_prepare(bev);
+    o.lo = z - h * m.z_center;
+    o.hi = z + h * (1.f - m.z_center);
+    o.size = o.b.area * h;                     // (dx dy) h
+    o.ok = (o.b.area == o.b.area && box_finite(z) && h >= 0.f && h < INFINITY) ? 1.f : 0.f;
+  }
+  return o;
+}
+
+PNP_FN OvBox box_no_box() {
+  OvBox o;
+  o.b = bev_no_box();
+  o.lo = o.hi = o.size = o.ok = 0.f;
+  return o;
+}
+
+template <int KIND>
+PNP_FN float box_pair(const OvBox& A, const OvBox& B, const OvMode& m) {
+#pragma clang fp contract(off)
+  float inter;
+  if (KIND == EPROPNP_BOX_IMAGE) {
+    const float iw = fminf(A.b.hx, B.b.hx) - fmaxf(A.b.cx, B.b.cx), ih = fminf(A.b.hy, B.b.hy) - fmaxf(A.b.cy, B.b.cy);
+    inter = (iw > 0.f && ih > 0.f) ? iw * ih : 0.f;
+  } else {
+    inter = bev_overlap_area(A.b, B.b);
+    if (KIND == EPROPNP_BOX_3D) {
+      // `interval`: the common part of the two height intervals.  `reference_torch`: the lower of the two bottoms where the higher
+      // belongs (bbox3d_iou_calculator.py:151 takes torch.min; its numpy twin at :90 np.maximum)
+      const float top = fminf(A.hi, B.hi);
+      const float bottom = (m.rule == EPROPNP_BOX_HEIGHT_INTERVAL) ? fmaxf(A.lo, B.lo) : fminf(A.lo, B.lo);
+      inter = inter * fmaxf(top - bottom, 0.f);
+    }
+  }
+  float v = inter;
+  if (m.crit != EPROPNP_BOX_CRIT_INTER) {
+    const float den = (m.crit == EPROPNP_BOX_CRIT_IOU) ? A.size + B.size - inter : (m.crit == EPROPNP_BOX_CRIT_A) ? A.size : B.size;
+    v = fminf(inter / fmaxf(den, 1e-8f), 1.f);
+  }
+  return (A.ok != 0.f && B.ok != 0.f) ? v : NAN;
+}
+
+// nrow x ncol pairs (1..64 each) of the boxes at a, b into out[r * stride + c]
+template <int KIND>
+PNP_FN void box_tile(const float* __restrict__ a, int nrow, const float* __restrict__ b, int ncol, const OvMode& m,
+                     float* __restrict__ out, int stride, OvBox* rows, OvBox* cols) {
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (wave == 0) cols[lane] = (lane < ncol) ? box_prepare<KIND>(b + (size_t)lane * box_floats<KIND>(), m) : box_no_box();
+  if (wave == 1) rows[lane] = (lane < nrow) ? box_prepare<KIND>(a + (size_t)lane * box_floats<KIND>(), m) : box_no_box();
+  __syncthreads();
+  const OvBox B = cols[lane];
+  if (lane >= ncol) return;
+  // one pair at a time, as in bev_overlap_kernel (build.py: no compiler-formed v_pk_*)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+  for (int r = wave; r < nrow; r += kBevOverlapThreads / 64) out[(size_t)r * (size_t)stride + lane] = box_pair<KIND>(rows[r], B, m);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBevOverlapThreads) void box_overlap_kernel(const float* __restrict__ boxes_a, int M,
+                                                                         const float* __restrict__ boxes_b, int N, OvMode m,
+                                                                         float* __restrict__ out) {
+  __shared__ OvBox rows[kBevTile], cols[kBevTile];
+  const int r0 = (int)blockIdx.y * kBevTile, c0 = (int)blockIdx.x * kBevTile;
+  box_tile<KIND>(boxes_a + (size_t)r0 * box_floats<KIND>(), min(kBevTile, M - r0), boxes_b + (size_t)c0 * box_floats<KIND>(),
+                 min(kBevTile, N - c0), m, out + (size_t)r0 * N + c0, N, rows, cols);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBevOverlapThreads) void box_overlap_aligned_kernel(const float* __restrict__ boxes_a,
+                                                                                 const float* __restrict__ boxes_b, int N, OvMode m,
+                                                                                 float* __restrict__ out) {
+  const long i = (long)blockIdx.x * kBevOverlapThreads + (long)threadIdx.x;
+  if (i >= N) return;
+  const OvBox A = box_prepare<KIND>(boxes_a + (size_t)i * box_floats<KIND>(), m);
+  const OvBox B = box_prepare<KIND>(boxes_b + (size_t)i * box_floats<KIND>(), m);
+  out[i] = box_pair<KIND>(A, B, m);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBevOverlapThreads) void box_overlap_segmented_kernel(const float* __restrict__ boxes_a, int M,
+                                                                                   const float* __restrict__ boxes_b, int N,
+                                                                                   const int32_t* __restrict__ tiles, OvMode m,
+                                                                                   float* __restrict__ out, long long num_out) {
+  __shared__ OvBox rows[kBevTile], cols[kBevTile];
+  const int32_t* t = tiles + (size_t)blockIdx.x * kBoxTileInts;
+  const int r0 = t[0], nrow = t[1], c0 = t[2], ncol = t[3], o0 = t[4], stride = t[5];
+  // the same for every thread of the workgroup: a tile outside the boxes or the output is skipped as a whole
+  const bool inside = nrow >= 1 && nrow <= kBevTile && ncol >= 1 && ncol <= kBevTile && r0 >= 0 && r0 <= M - nrow && c0 >= 0 &&
+                      c0 <= N - ncol && stride >= ncol && o0 >= 0 &&
+                      (long long)o0 + (long long)(nrow - 1) * (long long)stride + (long long)ncol <= num_out;
+  if (!inside) return;
+  box_tile<KIND>(boxes_a + (size_t)r0 * box_floats<KIND>(), nrow, boxes_b + (size_t)c0 * box_floats<KIND>(), ncol, m, out + o0, stride,
+                 rows, cols);
+}
+
+static int box_check(const char* who, int kind, int crit, int z_axis, float z_center, int rule) {
+  if (kind != EPROPNP_BOX_BEV && kind != EPROPNP_BOX_3D && kind != EPROPNP_BOX_IMAGE)
+    return fail(EPROPNP_EINVAL, "%s: unknown box kind %d", who, kind);
+  if (crit != EPROPNP_BOX_CRIT_IOU && crit != EPROPNP_BOX_CRIT_A && crit != EPROPNP_BOX_CRIT_B && crit != EPROPNP_BOX_CRIT_INTER)
+    return fail(EPROPNP_EINVAL, "%s: unknown criterion %d", who, crit);
+  if (rule != EPROPNP_BOX_HEIGHT_INTERVAL && rule != EPROPNP_BOX_HEIGHT_REFERENCE_TORCH)
+    return fail(EPROPNP_EINVAL, "%s: unknown height rule %d", who, rule);
+  if (kind == EPROPNP_BOX_3D && (z_axis < 0 || z_axis > 2)) return fail(EPROPNP_EINVAL, "%s: z_axis must be 0, 1 or 2, got %d", who, z_axis);
+  if (!(fabsf(z_center) < INFINITY)) return fail(EPROPNP_EINVAL, "%s: z_center is not finite", who);
+  return EPROPNP_OK;
+}
+
+int launch_box_overlap(const float* boxes_a, int M, const float* boxes_b, int N, int kind, int crit, int z_axis, float z_center,
+                       int rule, int aligned, float* out, hipStream_t st) {
+  const char* who = "epropnp_box_overlap";
+  if (M < 0 || N < 0) return fail(EPROPNP_EINVAL, "%s: box counts must be >= 0, got %d and %d", who, M, N);
+  if (aligned && M != N) return fail(EPROPNP_EINVAL, "%s: aligned needs num_a == num_b, got %d and %d", who, M, N);
+  if (int rc = box_check(who, kind, crit, z_axis, z_center, rule)) return rc;
+  if (M == 0 || N == 0) return EPROPNP_OK;
+  if (!boxes_a || !boxes_b || !out) return fail(EPROPNP_EINVAL, "%s: NULL pointer", who);
+  const OvMode m{crit, rule, kind == EPROPNP_BOX_3D ? z_axis : 0, z_center};
+  const dim3 block(kBevOverlapThreads);
+  if (aligned) {
+    const dim3 grid((unsigned)((N + kBevOverlapThreads - 1) / kBevOverlapThreads));
+    if (kind == EPROPNP_BOX_BEV) {
+      PNP_LAUNCH(box_overlap_aligned_kernel<EPROPNP_BOX_BEV>, grid, block, 0, st, boxes_a, boxes_b, N, m, out);
+    } else if (kind == EPROPNP_BOX_3D) {
+      PNP_LAUNCH(box_overlap_aligned_kernel<EPROPNP_BOX_3D>, grid, block, 0, st, boxes_a, boxes_b, N, m, out);
+    } else {
+      PNP_LAUNCH(box_overlap_aligned_kernel<EPROPNP_BOX_IMAGE>, grid, block, 0, st, boxes_a, boxes_b, N, m, out);
+    }
+    return check_launch("box_overlap_aligned_kernel");
+  }
+  const long rt = ((long)M + kBevTile - 1) / kBevTile, ct = ((long)N + kBevTile - 1) / kBevTile;
+  if (rt > 65535) return fail(EPROPNP_EINVAL, "%s: num_a = %d is more than %d rows of one launch", who, M, 65535 * kBevTile);
+  const dim3 grid((unsigned)ct, (unsigned)rt);
+  if (kind == EPROPNP_BOX_BEV) {
+    PNP_LAUNCH(box_overlap_kernel<EPROPNP_BOX_BEV>, grid, block, 0, st, boxes_a, M, boxes_b, N, m, out);
+  } else if (kind == EPROPNP_BOX_3D) {
+    PNP_LAUNCH(box_overlap_kernel<EPROPNP_BOX_3D>, grid, block, 0, st, boxes_a, M, boxes_b, N, m, out);
+  } else {
+    PNP_LAUNCH(box_overlap_kernel<EPROPNP_BOX_IMAGE>, grid, block, 0, st, boxes_a, M, boxes_b, N, m, out);
+  }
+  return check_launch("box_overlap_kernel");
+}
+
+int box_overlap_plan(const int32_t* counts_a, const int32_t* counts_b, int G, int32_t* tiles, long long capacity, long long* num_tiles,
+                     long long* num_out) {
+  const char* who = "epropnp_box_overlap_plan";
+  if (G < 0) return fail(EPROPNP_EINVAL, "%s: num_segments must be >= 0, got %d", who, G);
+  if (G > 0 && (!counts_a || !counts_b)) return fail(EPROPNP_EINVAL, "%s: NULL counts", who);
+  if (tiles && capacity < 0) return fail(EPROPNP_EINVAL, "%s: negative table capacity", who);
+  long long row = 0, col = 0, o = 0, nt = 0;
+  for (int g = 0; g < G; ++g) {
+    const long long na = counts_a[g], nb = counts_b[g];
+    if (na < 0 || nb < 0) return fail(EPROPNP_EINVAL, "%s: segment %d has negative counts %lld and %lld", who, g, na, nb);
+    if (row + na > INT32_MAX || col + nb > INT32_MAX) return fail(EPROPNP_EINVAL, "%s: more than 2^31 - 1 boxes", who);
+    if (o + na * nb > (long long)INT32_MAX)
+      return fail(EPROPNP_EINVAL, "%s: the output has 2^31 or more elements (segment %d: %lld x %lld)", who, g, na, nb);
+    for (long long r = 0; r < na && nb > 0; r += kBevTile)
+      for (long long c = 0; c < nb; c += kBevTile, ++nt) {
+        if (!tiles) continue;
+        if (nt >= capacity) return fail(EPROPNP_EINVAL, "%s: the table holds %lld tiles, more are needed", who, capacity);
+        int32_t* t = tiles + nt * kBoxTileInts;
+        t[0] = (int32_t)(row + r);
+        t[1] = (int32_t)(na - r < kBevTile ? na - r : kBevTile);
+        t[2] = (int32_t)(col + c);
+        t[3] = (int32_t)(nb - c < kBevTile ? nb - c : kBevTile);
+        t[4] = (int32_t)(o + r * nb + c);
+        t[5] = (int32_t)nb;
+      }
+    row += na; col += nb; o += na * nb;
+  }
+  if (num_tiles) *num_tiles = nt;
+  if (num_out) *num_out = o;
+  return EPROPNP_OK;
+}
+
+int launch_box_overlap_segmented(const float* boxes_a, int M, const float* boxes_b, int N, int kind, int crit, int z_axis,
+                                 float z_center, int rule, const int32_t* tiles, int num_tiles, float* out, long long num_out,
+                                 hipStream_t st) {
+  const char* who = "epropnp_box_overlap_segmented";
+  if (M < 0 || N < 0) return fail(EPROPNP_EINVAL, "%s: box counts must be >= 0, got %d and %d", who, M, N);
+  if (num_tiles < 0) return fail(EPROPNP_EINVAL, "%s: num_tiles must be >= 0, got %d", who, num_tiles);
+  if (num_out < 0 || num_out > (long long)INT32_MAX)
+    return fail(EPROPNP_EINVAL, "%s: num_out = %lld is outside 0 .. 2^31 - 1", who, num_out);
+  if (int rc = box_check(who, kind, crit, z_axis, z_center, rule)) return rc;
+  if (num_tiles == 0 || M == 0 || N == 0 || num_out == 0) return EPROPNP_OK;
+  if (!boxes_a || !boxes_b || !tiles || !out) return fail(EPROPNP_EINVAL, "%s: NULL pointer", who);
+  const OvMode m{crit, rule, kind == EPROPNP_BOX_3D ? z_axis : 0, z_center};
+  const dim3 grid((unsigned)num_tiles), block(kBevOverlapThreads);
+  if (kind == EPROPNP_BOX_BEV) {
+    PNP_LAUNCH(box_overlap_segmented_kernel<EPROPNP_BOX_BEV>, grid, block, 0, st, boxes_a, M, boxes_b, N, tiles, m, out, num_out);
+  } else if (kind == EPROPNP_BOX_3D) {
+    PNP_LAUNCH(box_overlap_segmented_kernel<EPROPNP_BOX_3D>, grid, block, 0, st, boxes_a, M, boxes_b, N, tiles, m, out, num_out);
+  } else {
+    PNP_LAUNCH(box_overlap_segmented_kernel<EPROPNP_BOX_IMAGE>, grid, block, 0, st, boxes_a, M, boxes_b, N, tiles, m, out, num_out);
+  }
+  return check_launch("box_overlap_segmented_kernel");
 }
 
 }  // namespace pnp

@@ -246,6 +246,30 @@ int epropnp_bev_nms(const float* boxes, const int32_t* order, const int32_t* gro
                              (hipStream_t)stream);
 }
 
+int epropnp_box_overlap(const float* boxes_a, int32_t num_a, const float* boxes_b, int32_t num_b, int32_t kind, int32_t criterion,
+                        int32_t z_axis, float z_center, int32_t height_rule, int32_t aligned, float* out, void* stream) {
+  pnp::StageScope prof_("box_overlap", (hipStream_t)stream);
+  return pnp::launch_box_overlap(boxes_a, num_a, boxes_b, num_b, kind, criterion, z_axis, z_center, height_rule, aligned, out,
+                                 (hipStream_t)stream);
+}
+
+int epropnp_box_overlap_plan(const int32_t* counts_a, const int32_t* counts_b, int32_t num_segments, int32_t* tiles,
+                             int64_t tiles_capacity, int64_t* num_tiles, int64_t* num_out) {
+  long long nt = 0, no = 0;
+  const int rc = pnp::box_overlap_plan(counts_a, counts_b, num_segments, tiles, tiles_capacity, &nt, &no);
+  if (rc == EPROPNP_OK && num_tiles) *num_tiles = nt;
+  if (rc == EPROPNP_OK && num_out) *num_out = no;
+  return rc;
+}
+
+int epropnp_box_overlap_segmented(const float* boxes_a, int32_t num_a, const float* boxes_b, int32_t num_b, int32_t kind,
+                                  int32_t criterion, int32_t z_axis, float z_center, int32_t height_rule, const int32_t* tiles,
+                                  int32_t num_tiles, float* out, int64_t num_out, void* stream) {
+  pnp::StageScope prof_("box_overlap_segmented", (hipStream_t)stream);
+  return pnp::launch_box_overlap_segmented(boxes_a, num_a, boxes_b, num_b, kind, criterion, z_axis, z_center, height_rule, tiles,
+                                           num_tiles, out, num_out, (hipStream_t)stream);
+}
+
 size_t epropnp_orient_density_scratch_bytes(int32_t mc_samples, int32_t num_obj) {
   return pnp::orient_density_scratch_bytes(mc_samples, num_obj);
 }

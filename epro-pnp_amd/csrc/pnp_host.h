@@ -292,6 +292,15 @@ int launch_bev_overlap(const float* boxes_a, int M, const float* boxes_b, int N,
 int launch_bev_nms(const float* boxes, const int32_t* order, const int32_t* group, int N, float thr, void* scratch,
                    size_t scratch_bytes, int32_t* keep_index, uint8_t* keep_mask, int32_t* num_keep, hipStream_t st);
 size_t bev_nms_scratch_bytes(int N);
+// rotated / 3D / image box overlaps under the four criteria (epropnp_box_overlap, _plan, _segmented): one launch each; the plan is a
+// host function that turns per-segment counts into the segmented launch's tile table
+int launch_box_overlap(const float* boxes_a, int M, const float* boxes_b, int N, int kind, int crit, int z_axis, float z_center,
+                       int rule, int aligned, float* out, hipStream_t st);
+int box_overlap_plan(const int32_t* counts_a, const int32_t* counts_b, int G, int32_t* tiles, long long capacity, long long* num_tiles,
+                     long long* num_out);
+int launch_box_overlap_segmented(const float* boxes_a, int M, const float* boxes_b, int N, int kind, int crit, int z_axis,
+                                 float z_center, int rule, const int32_t* tiles, int num_tiles, float* out, long long num_out,
+                                 hipStream_t st);
 // density_kernels.hip: density pictures of the weighted pose samples (epropnp_orient_density, epropnp_bev_density): one launch that
 // turns samples into weighted bins, one that sums them per 32 x 32 tile in LDS, box-filters and writes the picture
 int launch_orient_density(const float* pose, const float* logw, const float* pose_opt, int S, int B, int dof, int size, int kh,

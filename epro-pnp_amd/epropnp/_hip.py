@@ -103,6 +103,9 @@ def _declare(lib):
     lib.epropnp_bev_nms_scratch_bytes.argtypes = [i32]
     lib.epropnp_bev_nms_scratch_bytes.restype = C.c_size_t
     f32 = C.c_float
+    lib.epropnp_box_overlap.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp]
+    lib.epropnp_box_overlap_plan.argtypes = [vp, vp, i32, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.epropnp_box_overlap_segmented.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, i32, vp, i32, vp, C.c_int64, vp]
     lib.epropnp_orient_density.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     lib.epropnp_bev_density.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
     for name in ('orient', 'bev'):
@@ -163,7 +166,8 @@ def _declare(lib):
                  'posterior_modes', 'amis_forward_costs', 'monte_carlo_forward_costs', 'amis_backward_costs',
                  'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms', 'orient_density',
                  'bev_density', 'deform_sample_forward', 'deform_sample_backward', 'roi_logsumexp_forward',
-                 'roi_logsumexp_backward', 'roi_align_forward', 'roi_align_backward'):
+                 'roi_logsumexp_backward', 'roi_align_forward', 'roi_align_backward', 'box_overlap', 'box_overlap_plan',
+                 'box_overlap_segmented'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -188,7 +192,7 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_orient_density', 'epropnp_orient_density_scratch_bytes', 'epropnp_bev_density',
            'epropnp_bev_density_scratch_bytes', 'epropnp_deform_sample_forward', 'epropnp_deform_sample_backward',
            'epropnp_roi_logsumexp_forward', 'epropnp_roi_logsumexp_backward', 'epropnp_roi_align_forward',
-           'epropnp_roi_align_backward')
+           'epropnp_roi_align_backward', 'epropnp_box_overlap', 'epropnp_box_overlap_plan', 'epropnp_box_overlap_segmented')
 
 
 def lib():

@@ -356,6 +356,66 @@ int epropnp_bev_nms(const float* boxes /* (N,5) */, const int32_t* order /* (N,)
                     int32_t num_boxes, float iou_thr, void* scratch, size_t scratch_bytes, int32_t* keep_index /* (N,) */,
                     uint8_t* keep_mask /* (N,) */, int32_t* num_keep /* (1,) */, void* stream);
 
+/* Box overlaps under the reference's criteria: rotated, 3D and axis-aligned image boxes, pairwise, aligned or per segment -- what
+ * EPro-PnP-Det's numba-CUDA files compute (core/bbox_3d/iou_calculators/rotate_iou_kernel.py + bbox3d_iou_calculator.py for the
+ * score targets of score_type='iou', core/evaluation/kitti_utils/rotate_iou.py + eval.py: image_box_overlap, d3_box_overlap for
+ * calculate_iou_partly).  One pair function around the overlap routine above:
+ *   kind EPROPNP_BOX_BEV   five floats (cx, cy, dx, dy, angle): inter = the overlap area, size = dx * dy.
+ *   kind EPROPNP_BOX_3D    seven floats [x0, x1, x2, d0, d1, d2, ry]; the BEV box is the two centres and the two sizes that are not
+ *        z_axis's, in that order, and ry ([0, 2, 3, 5, 6] for z_axis = 1: the reference's bev_axes).  With z = x[z_axis], h = d[z_axis]:
+ *        lo = z - h * z_center, hi = z + h * (1 - z_center);  height rule EPROPNP_BOX_HEIGHT_INTERVAL: iw = max(min(hi_a, hi_b) -
+ *        max(lo_a, lo_b), 0);  EPROPNP_BOX_HEIGHT_REFERENCE_TORCH: iw = max(min(hi_a, hi_b) - min(lo_a, lo_b), 0), which is what the
+ *        reference's bev_to_box3d_overlaps_aligned_torch computes (bbox3d_iou_calculator.py:151 takes torch.min where the numpy twin at
+ *        :90 takes np.maximum) and what its training targets are built with.  inter = area * iw, size = (dx * dy) * h.
+ *   kind EPROPNP_BOX_IMAGE four floats (x1, y1, x2, y2): iw = min(x2) - max(x1), ih likewise, inter = iw * ih if both are > 0, else 0;
+ *        size = (x2 - x1) * (y2 - y1).
+ *   criterion EPROPNP_BOX_CRIT_IOU: inter / max(size_a + size_b - inter, 1e-8);  _A: inter / max(size_a, 1e-8);  _B: inter /
+ *        max(size_b, 1e-8), each through min(., 1);  _INTER: the raw area or volume.  The numbers are the reference's (-1, 0, 1, 2).
+ *        The 1e-8 floor is that of the IoU above; the reference's aligned functions floor at 1e-6 and its pairwise ones not at all: the
+ *        results differ only for boxes of zero size.
+ * A box is valid iff all its numbers are finite and its sizes are >= 0 (image: x2 >= x1 and y2 >= y1); the result is NaN exactly
+ * where either box is invalid.  Every output element is written.  Products are uncontracted: the three pairings give the same bits
+ * for the same pair, and kind BEV with _INTER gives the bits of epropnp_bev_overlap.  z_axis, z_center and height_rule are read for
+ * kind 3D only (and validated always).  No atomics, no allocation, no synchronisation; capturable into a hipGraph.
+ *
+ * epropnp_box_overlap: out (num_a, num_b) in 64 x 64 tiles, or with aligned != 0 (num_a == num_b) out (num_a,), the bits of the
+ * pairwise diagonal.  num_a == 0 or num_b == 0 launches nothing and follows no pointer.  EPROPNP_EINVAL: a negative count, aligned
+ * with num_a != num_b, an unknown kind / criterion / height rule, z_axis outside 0 .. 2 for kind 3D, a z_center that is not finite, a
+ * NULL pointer, num_a beyond 65535 tiles.
+ *
+ * epropnp_box_overlap_plan: a host function, no device work.  Segment g pairs the next counts_a[g] boxes of boxes_a with the next
+ * counts_b[g] boxes of boxes_b; its (counts_a[g], counts_b[g]) block lies row-major in one flat output, block after block.  The table
+ * has EPROPNP_BOX_TILE_INTS = 6 int32 per 64 x 64 tile: first row (index into boxes_a), rows in the tile (1 .. 64), first column
+ * (index into boxes_b), columns in the tile (1 .. 64), output index of the tile's first element, row stride (= counts_b[g]).  A
+ * segment with an empty side has no tiles.  With tiles == NULL only *num_tiles and *num_out are written (either may be NULL): the
+ * size query.  EPROPNP_EINVAL: num_segments < 0, NULL counts, a negative count, 2^31 or more boxes on a side or output elements, a
+ * table given with tiles_capacity (in tiles) below the tiles needed.
+ *
+ * epropnp_box_overlap_segmented: one launch, one workgroup per table entry; `tiles` (num_tiles, 6) is DEVICE memory, out has num_out
+ * elements.  An entry that points outside [0, num_a) x [0, num_b) or outside out is skipped: nothing is read or written out of
+ * bounds.  num_tiles == 0 (or no boxes, or num_out == 0) launches nothing and follows no pointer.  EPROPNP_EINVAL: a negative count,
+ * num_out outside 0 .. 2^31 - 1, an unknown kind / criterion / height rule, z_axis, z_center as above, a NULL pointer. */
+#define EPROPNP_BOX_BEV 0
+#define EPROPNP_BOX_3D 1
+#define EPROPNP_BOX_IMAGE 2
+#define EPROPNP_BOX_CRIT_IOU (-1)
+#define EPROPNP_BOX_CRIT_A 0
+#define EPROPNP_BOX_CRIT_B 1
+#define EPROPNP_BOX_CRIT_INTER 2
+#define EPROPNP_BOX_HEIGHT_INTERVAL 0
+#define EPROPNP_BOX_HEIGHT_REFERENCE_TORCH 1
+#define EPROPNP_BOX_TILE_INTS 6
+int epropnp_box_overlap(const float* boxes_a /* (num_a,5|7|4) */, int32_t num_a, const float* boxes_b /* (num_b,5|7|4) */,
+                        int32_t num_b, int32_t kind, int32_t criterion, int32_t z_axis, float z_center, int32_t height_rule,
+                        int32_t aligned, float* out /* (num_a,num_b) or (num_a,) */, void* stream);
+int epropnp_box_overlap_plan(const int32_t* counts_a /* (G,) host */, const int32_t* counts_b /* (G,) host */, int32_t num_segments,
+                             int32_t* tiles /* (tiles_capacity,6) host, or NULL */, int64_t tiles_capacity, int64_t* num_tiles,
+                             int64_t* num_out);
+int epropnp_box_overlap_segmented(const float* boxes_a, int32_t num_a, const float* boxes_b, int32_t num_b, int32_t kind,
+                                  int32_t criterion, int32_t z_axis, float z_center, int32_t height_rule,
+                                  const int32_t* tiles /* (num_tiles,6) device */, int32_t num_tiles, float* out /* (num_out,) */,
+                                  int64_t num_out, void* stream);
+
 /* Density pictures of the posterior, the weighted pose samples (S,B,P) + log-weights (S,B).  Both entries are one primitive -- a list
  * of weighted points (canvas, plane, pixel, weight) summed into pixels, then a zero-padded box sum of odd size -- in two launches:
  * one workgroup per object turns its samples into weights and bins; one workgroup per (canvas, 32 x 32 pixel tile) sums the points
@@ -416,7 +476,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "orient_density", "bev_density") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "box_overlap", "box_overlap_segmented", "orient_density", "bev_density") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
