@@ -150,13 +150,13 @@ PNP_FIT_FN void fit_translation(fit_t (&C)[3][3], const float* fallback_diag, fl
 
 // ---- the refit's reductions: NV per-lane partial sums -> NV totals, ONE wave, through LDS -------------------------------
 // A wave_sum per value costs 11 VALU instructions (4 DPP adds, 4 v_readlane, 3 adds: DPP and readlane issue at half rate),
-// 231 for the 21 moments of the 6-DoF refit -- on the one wave the other three of the workgroup are waiting for.  Transposed
+// 165 for the 15 moments of the 6-DoF refit's first pass -- on the one wave the other three of the workgroup are waiting for.  Transposed
 // instead: every lane parks its NV partials (row v, column = lane: NV ds_write), lane 4 v' + j then adds columns
 // [16 j, 16 j + 16) of row v = base + v' (4 ds_read_b128, 15 adds), two quad-DPP adds join the four quarters, and the NV
-// totals come back as broadcast reads: ~35 VALU instructions for 21 values.  Fixed order: bit-reproducible.
+// totals come back as broadcast reads: ~35 VALU instructions for 21 values (the scratch keeps the 21 rows it was laid out for).  Fixed order: bit-reproducible.
 constexpr int kRefitMaxVals = 21;
 constexpr int kRefitRedFloats = kRefitMaxVals * kSumTRow + 24;     // rows of 64 + 4 floats, then the totals
-// The same reductions in a scratch of 11 rows: the 21 moments go through it as 11 + 10 (amis_refit<DOF, true>).  A row's sum does not
+// The same reductions in a scratch of 11 rows: the 15 moments go through it as 11 + 4 (amis_refit<DOF, true>).  A row's sum does not
 // depend on which rows share its pass -- the same four lane quarters add the same 16 columns each in the same order --, so the totals
 // keep their bits.
 constexpr int kRefitHalfVals = 11;
@@ -192,6 +192,77 @@ PNP_FN void wave_sum_t(float (&v)[NV], float* lds, int lane) {
 template <int NV, int ROWS = kRefitMaxVals>
 PNP_FN void refit_sum(float (&v)[NV], float* scratch, int lane) {
   wave_sum_t<NV, ROWS>(v, scratch, lane);
+}
+
+// Sum over the 64 lanes of NV values in the precision of the fits, result in every lane, through the same scratch (the half-size one
+// suffices): lane 8 v + j adds columns [8 j, 8 j + 8) of row v, lane v then the row's eight partials.  Fixed order: bit-reproducible,
+// and it does not depend on the size of the scratch.
+template <int NV>
+PNP_FN void wave_sum_fit(fit_t (&v)[NV], float* lds, int lane) {
+  static_assert(NV <= 8 && NV * 64 * sizeof(fit_t) <= kRefitHalfFloats * sizeof(float), "one row of 64 per value, eight lanes per row");
+  fit_t* row = reinterpret_cast<fit_t*>(lds);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) row[i * 64 + lane] = v[i];
+  wave_lds_fence();
+  if (lane < 8 * NV) {
+    fit_t* r = row + 8 * lane;
+    r[0] = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  }
+  wave_lds_fence();
+  if (lane < NV) {
+    fit_t* r = row + 64 * lane;
+    r[0] = ((r[0] + r[8]) + (r[16] + r[24])) + ((r[32] + r[40]) + (r[48] + r[56]));
+  }
+  wave_lds_fence();
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = row[64 * i];
+  wave_lds_fence();
+}
+
+// The refit's translation covariance (lower triangle, tri order), one wave: a second pass over the M samples centred on the new
+// mean `mu`, as the reference's is (epropnp.py:240-243 / :319-322), accumulated in the precision of the Cholesky that takes it, with
+// the residual first moment removed (mu is a rounded fp32 mean; sum e dev dev^T / Z - delta delta^T does not depend on where
+// exactly the centre sits).  Formed in the first pass as E[dd^T] - dd^T about the previous mode it cancelled once one sample held
+// nearly all the weight (an overconfident pose_cov, an unconverged start): covariances off by 1e-3 .. 1e-1, Cholesky fallbacks to
+// the 1 m default where the reference has none.  And fp32 entries cannot hold a covariance whose condition exceeds 1e7 -- two
+// samples sharing the weight, the rest at 1e-6 -- however they are summed: rounded to fp32 it is indefinite half of the time.
+PNP_FN void refit_translation_cov(const AmisParams& a, const float* smp, const float* lgw, int S, int M, float mx, float mu0, float mu1,
+                                  float mu2, float invZ, float* scratch, int lane, fit_t (&C)[6]) {
+  fit_t dl[3];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) C[i] = fit_t(0);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) dl[i] = fit_t(0);
+  if (PNP_ABLATED(a, 8)) C[0] = C[2] = C[5] = fit_t(1);
+  else
+  for (int m = lane; m < M; m += 64) {
+    const float e = fast_exp(lgw[m] - mx);
+    const fit_t d0 = (fit_t)(smp[m] - mu0), d1 = (fit_t)(smp[S + m] - mu1), d2 = (fit_t)(smp[2 * S + m] - mu2);
+    const fit_t e0 = (fit_t)e * d0, e1 = (fit_t)e * d1, e2 = (fit_t)e * d2;
+    dl[0] += e0; dl[1] += e1; dl[2] += e2;
+    C[0] += e0 * d0; C[1] += e1 * d0; C[2] += e1 * d1;
+    C[3] += e2 * d0; C[4] += e2 * d1; C[5] += e2 * d2;
+  }
+  if (!PNP_ABLATED(a, 16)) {
+    wave_sum_fit<6>(C, scratch, lane);
+    wave_sum_fit<3>(dl, scratch, lane);
+  }
+  const fit_t iz = (fit_t)invZ;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) dl[i] *= iz;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) C[tri(i, j)] = C[tri(i, j)] * iz - dl[i] * dl[j];
+  // Fewer than four samples with any weight (s = 3; one sample at 1 - 1e-20): the covariance is singular in exact arithmetic and
+  // its last pivots are rounding residue of either sign -- by chance the fallback, or a factor of condition 1e8 whose inverse no
+  // fp32 density can use.  A pivot below 1e-12 of its diagonal entry (the residue is ~1e-15) is none: NaN, the factorisation fails,
+  // the default factor is taken as for an indefinite matrix.
+  const fit_t tol = fit_t(1e-12);
+  const fit_t l21 = C[4] - C[3] * C[1] / C[0];
+  const fit_t p1 = C[2] - C[1] * C[1] / C[0];
+  const fit_t p2 = C[5] - C[3] * C[3] / C[0] - l21 * l21 / p1;
+  if (p1 <= tol * C[2] || p2 <= tol * C[5]) C[0] = fit_t(NAN);
 }
 
 // Translation (3x3) and rotation (4x4, ACG) factors of a proposal fitted by TWO lanes in lockstep: lane 0 takes the rotation
@@ -676,7 +747,7 @@ PNP_FN void amis_weights(const AmisCtx& cx, const AmisParams& a, int it, int WP)
 // Runs on wave 0 only: with <= a few hundred samples the moment passes are short, and a single wave needs no workgroup
 // barriers (the other waves pre-generate the next draw's base noise and wait at the end).  What the phase costs is the
 // number of instructions that one wave issues while three are parked (profiles/r02_tune_fwd_serial_phases.txt, r04): the
-// cross-lane sums go through LDS transposed (wave_sum_t: ~35 instead of 231 VALU instructions for the 21 moments), the
+// cross-lane sums go through LDS transposed (wave_sum_t: ~35 VALU instructions where a wave_sum per moment took 11 each), the
 // fixed point hands the samples the Cholesky factor L of Sigma instead of Sigma^-1 (|L^-1 q|^2 = q^T Sigma^-1 q by forward
 // substitution: no triangular inverse and no L^-T L^-1 product on the fitting lane, 14 instead of 20 operations per sample,
 // and a sum of squares instead of a cancelling quadratic form), the weights
@@ -705,60 +776,57 @@ PNP_FN void amis_refit(const AmisCtx& cx, const AmisParams& a, int it) {
     __syncthreads();
     return;
   }
-  // One pass over the samples gathers every first/second moment that does not depend on a matrix inverse:
-  // Z = sum e, sum e d, sum e d d^T with d = t - (previous mode) as pivot (keeps the E[dd^T] - dd^T cancellation
-  // benign), and -- since the ACG fixed point starts from Sigma = I -- the first maximum-likelihood step as well.
+  // A first pass over the samples gathers Z = sum e, the mean as sum e d with d = t - (previous mode) as pivot, and -- since the
+  // ACG fixed point starts from Sigma = I -- the first maximum-likelihood step; the translation covariance takes a second pass
+  // centred on that mean (refit_translation_cov).
   float mx = -INFINITY;
   for (int m = tid; m < M; m += T) mx = fmaxf(mx, lgw[m]);
   mx = wave_max(mx);
   const float p0 = rec[0], p1 = rec[1], p2 = rec[2];
   if (DOF == 6) {
-    float mom[21];
+    float mom[15];      // Z | sum e d | sum iw q q^T (lower triangle) | sum iw
 #pragma unroll
-    for (int i = 0; i < 21; ++i) mom[i] = 0.f;
-    if (PNP_ABLATED(a, 8)) mom[0] = mom[4] = mom[6] = mom[9] = mom[10] = mom[12] = mom[15] = mom[19] = mom[20] = 1.f;
+    for (int i = 0; i < 15; ++i) mom[i] = 0.f;
+    if (PNP_ABLATED(a, 8)) mom[0] = mom[4] = mom[6] = mom[9] = mom[13] = mom[14] = 1.f;
     else
     for (int m = tid; m < M; m += T) {
       const float e = fast_exp(lgw[m] - mx);
       const float d0 = smp[m] - p0, d1 = smp[S + m] - p1, d2 = smp[2 * S + m] - p2;
       mom[0] += e;
       mom[1] += e * d0; mom[2] += e * d1; mom[3] += e * d2;
-      mom[4] += e * d0 * d0; mom[5] += e * d1 * d0; mom[6] += e * d1 * d1;
-      mom[7] += e * d2 * d0; mom[8] += e * d2 * d1; mom[9] += e * d2 * d2;
       const float q0 = smp[3 * S + m], q1 = smp[4 * S + m], q2 = smp[5 * S + m], q3 = smp[6 * S + m];
       const float iw = e * fast_rcp(fmaxf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3, a.eps));    // M = q^T I q
-      mom[10] += iw * q0 * q0;
-      mom[11] += iw * q1 * q0; mom[12] += iw * q1 * q1;
-      mom[13] += iw * q2 * q0; mom[14] += iw * q2 * q1; mom[15] += iw * q2 * q2;
-      mom[16] += iw * q3 * q0; mom[17] += iw * q3 * q1; mom[18] += iw * q3 * q2; mom[19] += iw * q3 * q3;
-      mom[20] += iw;
+      mom[4] += iw * q0 * q0;
+      mom[5] += iw * q1 * q0; mom[6] += iw * q1 * q1;
+      mom[7] += iw * q2 * q0; mom[8] += iw * q2 * q1; mom[9] += iw * q2 * q2;
+      mom[10] += iw * q3 * q0; mom[11] += iw * q3 * q1; mom[12] += iw * q3 * q2; mom[13] += iw * q3 * q3;
+      mom[14] += iw;
     }
     if (!PNP_ABLATED(a, 16)) {
       if constexpr (HALF) {
-        float lo[11], hi[10];
+        float lo[11], hi[4];
 #pragma unroll
         for (int i = 0; i < 11; ++i) lo[i] = mom[i];
 #pragma unroll
-        for (int i = 0; i < 10; ++i) hi[i] = mom[11 + i];
+        for (int i = 0; i < 4; ++i) hi[i] = mom[11 + i];
         refit_sum<11, ROWS>(lo, cx.rred, tid);
-        refit_sum<10, ROWS>(hi, cx.rred, tid);
+        refit_sum<4, ROWS>(hi, cx.rred, tid);
 #pragma unroll
         for (int i = 0; i < 11; ++i) mom[i] = lo[i];
 #pragma unroll
-        for (int i = 0; i < 10; ++i) mom[11 + i] = hi[i];
+        for (int i = 0; i < 4; ++i) mom[11 + i] = hi[i];
       } else {
-        refit_sum<21>(mom, cx.rred, tid);
+        refit_sum<15>(mom, cx.rred, tid);
       }
     }
     const float invZ = 1.0f / mom[0];
     const float dl0 = mom[1] * invZ, dl1 = mom[2] * invZ, dl2 = mom[3] * invZ;
     const float mu0 = p0 + dl0, mu1 = p1 + dl1, mu2 = p2 + dl2;
-    float c6[6];
-    c6[0] = mom[4] * invZ - dl0 * dl0; c6[1] = mom[5] * invZ - dl1 * dl0; c6[2] = mom[6] * invZ - dl1 * dl1;
-    c6[3] = mom[7] * invZ - dl2 * dl0; c6[4] = mom[8] * invZ - dl2 * dl1; c6[5] = mom[9] * invZ - dl2 * dl2;
+    fit_t c6[6];
+    refit_translation_cov(a, smp, lgw, S, M, mx, mu0, mu1, mu2, invZ, cx.rred, tid, c6);
     float acc[11];
 #pragma unroll
-    for (int i = 0; i < 11; ++i) acc[i] = mom[10 + i];
+    for (int i = 0; i < 11; ++i) acc[i] = mom[4 + i];
     PNP_REFIT_PHASE(0);
     float Lf[10], Ld[4];
     for (int r = 1; r < a.mle_iter; ++r) {
@@ -823,7 +891,7 @@ PNP_FN void amis_refit(const AmisCtx& cx, const AmisParams& a, int it) {
         for (int j = 0; j <= i; ++j) {
           fit_t v = (a.mle_iter > 0) ? (fit_t)acc[tri(i, j)] * inorm + ((i == j) ? (fit_t)a.eps : fit_t(0))
                                       : ((i == j) ? fit_t(1) : fit_t(0));
-          if (tid == 1) v = (i < 3) ? (fit_t)c6[tri(i, j)] : ((i == j) ? fit_t(1) : fit_t(0));
+          if (tid == 1) v = (i < 3) ? c6[tri(i, j)] : ((i == j) ? fit_t(1) : fit_t(0));
           A4[i][j] = v;
           A4[j][i] = v;
         }
@@ -832,31 +900,27 @@ PNP_FN void amis_refit(const AmisCtx& cx, const AmisParams& a, int it) {
     }
     PNP_REFIT_PHASE(2);
   } else {
-    float mom[12];
+    float mom[6];       // Z | sum e d | sum e sin yaw, sum e cos yaw
 #pragma unroll
-    for (int i = 0; i < 12; ++i) mom[i] = 0.f;
+    for (int i = 0; i < 6; ++i) mom[i] = 0.f;
     for (int m = tid; m < M; m += T) {
       const float e = fast_exp(lgw[m] - mx);
       const float d0 = smp[m] - p0, d1 = smp[S + m] - p1, d2 = smp[2 * S + m] - p2;
       mom[0] += e;
       mom[1] += e * d0; mom[2] += e * d1; mom[3] += e * d2;
-      mom[4] += e * d0 * d0; mom[5] += e * d1 * d0; mom[6] += e * d1 * d1;
-      mom[7] += e * d2 * d0; mom[8] += e * d2 * d1; mom[9] += e * d2 * d2;
       const float yaw = smp[3 * S + m];
       float sy, cy;
       sincos_rad(yaw, sy, cy);
-      mom[10] += e * sy;
-      mom[11] += e * cy;
+      mom[4] += e * sy;
+      mom[5] += e * cy;
     }
-    refit_sum<12>(mom, cx.rred, tid);
+    refit_sum<6>(mom, cx.rred, tid);
     const float invZ = 1.0f / mom[0];
     const float dl0 = mom[1] * invZ, dl1 = mom[2] * invZ, dl2 = mom[3] * invZ;
     const float mu0 = p0 + dl0, mu1 = p1 + dl1, mu2 = p2 + dl2;
-    float c8[8];
-    c8[0] = mom[4] * invZ - dl0 * dl0; c8[1] = mom[5] * invZ - dl1 * dl0; c8[2] = mom[6] * invZ - dl1 * dl1;
-    c8[3] = mom[7] * invZ - dl2 * dl0; c8[4] = mom[8] * invZ - dl2 * dl1; c8[5] = mom[9] * invZ - dl2 * dl2;
-    c8[6] = mom[10] * invZ;
-    c8[7] = mom[11] * invZ;
+    fit_t c6[6];
+    refit_translation_cov(a, smp, lgw, S, M, mx, mu0, mu1, mu2, invZ, cx.rred, tid, c6);
+    const float ms = mom[4] * invZ, mc = mom[5] * invZ;
     if (tid == 0) {
       nrec[0] = mu0; nrec[1] = mu1; nrec[2] = mu2;
       fit_t Ct[3][3];
@@ -864,14 +928,14 @@ PNP_FN void amis_refit(const AmisCtx& cx, const AmisParams& a, int it) {
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j <= i; ++j) {
-          Ct[i][j] = (fit_t)c8[tri(i, j)];
-          Ct[j][i] = (fit_t)c8[tri(i, j)];
+          Ct[i][j] = c6[tri(i, j)];
+          Ct[j][i] = c6[tri(i, j)];
         }
       const float dflt[3] = {1.f, 1.f, 4.f};
       nrec[38] = nrec[39] = 0.f;
       fit_translation(Ct, dflt, nrec);
-      nrec[16] = atan2f(c8[6], c8[7]);
-      const float r_sq = c8[6] * c8[6] + c8[7] * c8[7];
+      nrec[16] = atan2f(ms, mc);
+      const float r_sq = ms * ms + mc * mc;
       const float kappa = 0.33f * fmaxf(sqrtf(r_sq), a.eps) * (2.f - r_sq) / fmaxf(1.f - r_sq, a.eps);
       nrec[17] = kappa;
       nrec[18] = log_i0(kappa);

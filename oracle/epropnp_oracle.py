@@ -573,6 +573,151 @@ def amis(x3d, x2d, w2d, cam, delta, pose_opt, pose_cov, noise, mc_samples=512, n
     return pose_samples, logweights
 
 
+# ----------------------------------------------------------------------------------------
+# the AMIS refit, one step at a time, against an implementation's own proposal records
+# ----------------------------------------------------------------------------------------
+
+# proposal record of the kernels (csrc/amis_common.h: kPropStride): [0..2] mode | [3..8] L_t, lower triangle packed row by row |
+# 6-DoF [16..25] L_r likewise | 4-DoF [16] yaw mode, [17] kappa | [37] 1 if the translation factor is the default
+REFIT_FIELDS = {6: ('mode', 'L_t', 'L_r'), 4: ('mode', 'L_t', 'rmode', 'kappa')}
+REFIT_RELATIVE = ('L_t', 'L_r', 'kappa')       # compared relative to the object's largest entry; mode / rmode absolutely
+COST_BAR = (2e-5, 1e-5)                        # rtol, atol of a fp32 cost against the fp64 one (test_evaluate_cost_matches_reference)
+
+
+def tril_unpack(v, n):
+    """(..., n (n + 1) / 2) packed lower triangle, row by row -> (..., n, n)"""
+    L = v.new_zeros(v.shape[:-1] + (n, n))
+    idx = torch.tril_indices(n, n)
+    L[..., idx[0], idx[1]] = v
+    return L
+
+
+def tril_pack(L):
+    idx = torch.tril_indices(L.shape[-1], L.shape[-1])
+    return L[..., idx[0], idx[1]]
+
+
+def record_fields(rec, dof):
+    """the fitted quantities of proposal records (..., 40), keyed as REFIT_FIELDS + 'fallback'"""
+    out = dict(mode=rec[..., 0:3], L_t=tril_unpack(rec[..., 3:9], 3), fallback=rec[..., 37] != 0)
+    if dof == 6:
+        out['L_r'] = tril_unpack(rec[..., 16:26], 4)
+    else:
+        out['rmode'], out['kappa'] = rec[..., 16:17], rec[..., 17:18]
+    return out
+
+
+def pack_records(props, dof):
+    """`amis(..., return_proposals=True)`'s dict -> records (B,K,40) with the slots of record_fields filled (slot 37 stays 0)"""
+    K, B = props['mode'].shape[:2]
+    rec = props['mode'].new_zeros(B, K, 40)
+    rec[..., 0:3] = props['mode'].transpose(0, 1)
+    rec[..., 3:9] = tril_pack(props['L_t']).transpose(0, 1)
+    if dof == 6:
+        rec[..., 16:26] = tril_pack(props['L_r']).transpose(0, 1)
+    else:
+        rec[..., 16:17], rec[..., 17:18] = props['rmode'].transpose(0, 1), props['kappa'].transpose(0, 1)
+    return rec
+
+
+def records_mixture_logq(samples, records, dof, n):
+    """log density of the equal-weight mixture of records 0 .. n-1 (B,K,40) at samples (M,B,p)   (epropnp.py:156-165)"""
+    lq = []
+    for j in range(n):
+        f = record_fields(records[:, j], dof)
+        lp = student_t_logprob(samples[..., :3], f['mode'], f['L_t'])
+        if dof == 6:
+            lp = lp + acg_logprob(samples[..., 3:], f['L_r'])
+        else:
+            lp = lp + vm_mix_logprob(samples[..., 3:], f['rmode'], f['kappa']).squeeze(-1)
+        lq.append(lp)
+    return torch.logsumexp(torch.stack(lq, 0), 0) - math.log(n)
+
+
+def refit_field_diff(a, b, key):
+    """per object (leading axis): max |a - b|; relative to the object's largest |b| for REFIT_RELATIVE; yaw modulo 2 pi"""
+    a, b = a.double(), b.double()
+    d = (a - b).abs()
+    if key == 'rmode':
+        d = torch.minimum(d, 2 * math.pi - d)
+    d = d.reshape(d.shape[0], -1).amax(1)
+    if key in REFIT_RELATIVE:
+        d = d / b.abs().reshape(b.shape[0], -1).amax(1).clamp(min=1e-30)
+    return d
+
+
+def estimate_fields(dof, samples, logw, eps=1e-5, acg_mle_iter=3, acg_dispersion=0.001):
+    """estimate_6dof / estimate_4dof as a dict keyed as REFIT_FIELDS"""
+    if dof == 6:
+        return dict(zip(REFIT_FIELDS[6], estimate_6dof(samples, logw, eps, acg_mle_iter, acg_dispersion)))
+    return dict(zip(REFIT_FIELDS[4], estimate_4dof(samples, logw, eps)))
+
+
+def took_default(L_t, dof):
+    """whether chol_or_default returned the default factor (a fitted factor never equals it entry for entry)"""
+    dflt = torch.eye(3, dtype=L_t.dtype) if dof == 6 else torch.diag(torch.tensor([1.0, 1.0, 4.0], dtype=L_t.dtype))
+    return (L_t == dflt).all(-1).all(-1)
+
+
+@torch.no_grad()
+def refit_steps(prob, dof, samples, records, noise, num_iter, eps=1e-5, acg_mle_iter=3, acg_dispersion=0.001,
+                trials=8, ulps=3, seed=1000):
+    """The adaptive part of the AMIS loop (epropnp.py:165-175) restated in fp64 ONE REFIT AT A TIME from an implementation's
+    own outputs -- samples (S,B,p), proposal records (B,K,40) -- so that every refit is judged on the inputs it really had.
+
+    For i = 0 .. K-2: log-weights of the first (i+1) s samples = -(fp64 cost) - (equal-weight mixture of the implementation's
+    records 0 .. i), then estimate_6dof / estimate_4dof -> what record i+1 should hold; and the samples of block i+1 drawn from
+    the implementation's record i+1 with the injected noise.
+
+    Yardstick per field, refit and object, from the reference alone: the larger of |fp32 run - fp64 run| of the same estimate
+    and how far the fp64 run moves over `trials` perturbed inputs -- samples by <= `ulps` ulp (perturb_inputs' rule),
+    log-weights by uniform noise of amplitude 2e-5 |cost| + 1e-5 (COST_BAR: what a fp32 cost is entitled to).
+
+    -> dict: expect {field: (K-1,B,..)}, spread {field: (K-1,B)}, fallback (K-1,B) bool, ess (K-1,B), logw [K-1 x ((i+1)s,B)],
+             draws ((K-1)s,B,p): blocks 1 .. K-1"""
+    S, B, _ = samples.shape
+    K, s = num_iter, samples.shape[0] // num_iter
+    smp, rec = samples.double(), records.double()
+    cam = Cam(prob['cam_mats'].double(), float(prob.get('z_min', 0.1)),
+              *(prob[k].double() if k in prob else None for k in ('lb', 'ub')))
+    cost = evaluate(prob['x3d'].double(), prob['x2d'].double(), prob['w2d'].double(), smp, cam, prob['delta'].double(),
+                    want_cost=True)[1]
+    kw = dict(eps=eps, acg_mle_iter=acg_mle_iter, acg_dispersion=acg_dispersion)
+    g = torch.Generator().manual_seed(seed)
+    fields = REFIT_FIELDS[dof]
+    expect, spread = {k: [] for k in fields}, {k: [] for k in fields}
+    fallback, ess, logws, draws = [], [], [], []
+    for i in range(K - 1):
+        M = (i + 1) * s
+        lw = -cost[:M] - records_mixture_logq(smp[:M], rec, dof, i + 1)
+        e64 = estimate_fields(dof, smp[:M], lw, **kw)
+        e32 = estimate_fields(dof, smp[:M].float(), lw.float(), **kw)
+        sp = {k: refit_field_diff(e32[k], e64[k], k) for k in fields}
+        amp = COST_BAR[0] * cost[:M].abs() + COST_BAR[1]
+        for _ in range(trials):
+            kk = torch.randint(-ulps, ulps + 1, smp[:M].shape, generator=g).double()
+            jit = (torch.rand(lw.shape, generator=g, dtype=torch.float64) * 2 - 1) * amp
+            et = estimate_fields(dof, smp[:M] * (1 + kk * 2.0 ** -23), lw + jit, **kw)
+            for k in fields:
+                sp[k] = torch.maximum(sp[k], refit_field_diff(et[k], e64[k], k))
+        for k in fields:
+            expect[k].append(e64[k])
+            spread[k].append(sp[k])
+        w = torch.softmax(lw, dim=0)
+        ess.append(1.0 / (w * w).sum(0))
+        fallback.append(took_default(e64['L_t'], dof))
+        logws.append(lw)
+        f = record_fields(rec[:, i + 1], dof)
+        t = student_t_sample(f['mode'], f['L_t'], noise['z'][i + 1].double(), noise['chi2'][i + 1].double())
+        if dof == 6:
+            r = acg_sample(f['L_r'], noise['g'][i + 1].double())
+        else:
+            r = vm_mix_sample(f['rmode'], f['kappa'], noise['u'][i + 1].double(), noise['vm'][i + 1].double(), s)
+        draws.append(torch.cat((t, r), -1))
+    return dict(expect={k: torch.stack(v) for k, v in expect.items()}, spread={k: torch.stack(v) for k, v in spread.items()},
+                fallback=torch.stack(fallback), ess=torch.stack(ess), logw=logws, draws=torch.cat(draws, 0))
+
+
 def monte_carlo_forward(x3d, x2d, w2d, cam, delta, pose_init, noise, mc_samples=512, num_iter=4,
                         lm_kw=None, normalize=False, fast_mode=False, with_pose_opt_plus=False,
                         rslm_noise=None, rslm_kw=None, eps=1e-5):
