@@ -55,6 +55,53 @@ def make_layer_objects(prob, device, relative_delta=None):
     return p, cam, cf
 
 
+CAMERA_KINDS = ('per_object', 'skewed', 'full')
+
+
+def vary_cameras(prob, kind, seed):
+    """A copy of an `orc.make_problem` dict in which every object has its own camera matrix (make_problem expands ONE
+    matrix over the batch; its random stream is not touched: the draws here come from a generator of their own).
+
+      'per_object'  fx, fy independent in [500, 1400], cx in [200, 900], cy in [150, 500], third row (0, 0, 1)
+      'skewed'      + K[0,1] in +-30, K[1,0] in +-20, fx negated (horizontal flip) for every second object
+      'full'        + K[2,0], K[2,1] in +-0.05 (a rectifying homography), the whole matrix times its own factor in [0.5, 2.5]
+
+    x2d is re-projected in fp64 from x3d and pose_gt through the new matrices and keeps the pixel noise make_problem drew (what
+    x2d was off its own noise-free projection by); delta is recomputed; bounds, where the input has them, become the 5 % / 95 %
+    quantiles of each object's own x2d (about 10 % of the points clipped per axis: a fixed box under wandering principal
+    points clips most points, whose zero Jacobians leave the normal equations near-singular)."""
+    assert kind in CAMERA_KINDS, kind
+    g = torch.Generator().manual_seed(seed)
+    dtype = prob['x2d'].dtype
+    B = prob['x2d'].shape[0]
+    uni = lambda lo, hi: lo + (hi - lo) * torch.rand(B, generator=g, dtype=torch.float64)
+    K = torch.zeros(B, 3, 3, dtype=torch.float64)
+    K[:, 0, 0], K[:, 1, 1] = uni(500, 1400), uni(500, 1400)
+    K[:, 0, 2], K[:, 1, 2] = uni(200, 900), uni(150, 500)
+    K[:, 2, 2] = 1.0
+    if kind in ('skewed', 'full'):
+        K[:, 0, 1], K[:, 1, 0] = uni(-30, 30), uni(-20, 20)
+        K[1::2, 0, 0] *= -1.0
+    if kind == 'full':
+        K[:, 2, 0], K[:, 2, 1] = uni(-0.05, 0.05), uni(-0.05, 0.05)
+        K *= uni(0.5, 2.5).reshape(B, 1, 1)
+    x3d, pose_gt = prob['x3d'].double(), prob['pose_gt'].double()
+    px_noise = prob['x2d'].double() - orc.evaluate_project(x3d, pose_gt, orc.Cam(prob['cam_mats'].double(), 0.1))
+    out = dict(prob)
+    out['cam_mats'] = K.to(dtype).contiguous()
+    out['x2d'] = (orc.evaluate_project(x3d, pose_gt, orc.Cam(K, 0.1)) + px_noise).to(dtype)
+    out['delta'] = orc.adaptive_huber_delta(out['x2d'], out['w2d'], 0.5)
+    if 'lb' in prob:
+        q = torch.quantile(out['x2d'].double(), torch.tensor([0.05, 0.95], dtype=torch.float64), dim=1)      # (2,B,2)
+        out['lb'], out['ub'] = q[0].to(dtype).contiguous(), q[1].to(dtype).contiguous()
+    for k in ('cam_mats', 'lb', 'ub'):
+        if k in out:
+            flat = out[k].reshape(B, -1)
+            same = (flat.unsqueeze(0) == flat.unsqueeze(1)).all(-1) & ~torch.eye(B, dtype=torch.bool)
+            assert not bool(same.any()), f'{k}: two objects share a value'
+    return out
+
+
 def assert_within_spread(err, spread, bar, k=2.0, what=''):
     """Parity bar with the reference's own rounding sensitivity as the yardstick, compared as ORDER STATISTICS over the
     objects of the batch: the i-th largest error must not exceed `bar + k x` the i-th largest spread.

@@ -489,6 +489,28 @@ def test_camera_view_cache_tracks_the_camera_state(backend):
     cam2.ub = 300.0
     c_b2 = F.evaluate_cost(F.PnPProblem(d['x3d'], d['x2d'], d['w2d'], cam2, cf, 6), pose)
     assert torch.isfinite(c_b).all() and (c_b2 - c_b).abs().max() > 0
+    # per-object contiguous cam_mats, edited in place in ONE object's row: only that object's result changes, to the oracle's value
+    from helpers import vary_cameras
+    pv = vary_cameras(p, 'skewed', seed=2)
+    dv, cam3, _ = make_layer_objects(pv, backend)
+    assert cam3.cam_mats.is_contiguous() and cam3.cam_mats.shape == (3, 3, 3)
+
+    def cost3():
+        return F.evaluate_cost(F.PnPProblem(dv['x3d'], dv['x2d'], dv['w2d'], cam3, cf, 6), pose).clone()
+
+    def oracle3():
+        q = {k: (v.double() if isinstance(v, torch.Tensor) else v) for k, v in pv.items()}
+        return orc.evaluate(q['x3d'], q['x2d'], q['w2d'], q['pose_init'], orc.Cam(cam3.cam_mats.detach().cpu().double(), 0.1), p['delta'].double(),
+                            want_cost=True)[1]
+    c3 = cost3()
+    torch.testing.assert_close(cost3(), c3, rtol=0, atol=0)                    # cached views
+    torch.testing.assert_close(c3.cpu().double(), oracle3(), rtol=2e-5, atol=1e-5)
+    with torch.no_grad():
+        cam3.cam_mats[1, 0, 2] += 7.0                                          # object 1's principal point, same tensor object
+        cam3.cam_mats[1, 1, 0] -= 3.0
+    c4 = cost3()
+    assert torch.equal(c4[0], c3[0]) and torch.equal(c4[2], c3[2]) and abs(float(c4[1] - c3[1])) > 1e-3
+    torch.testing.assert_close(c4.cpu().double(), oracle3(), rtol=2e-5, atol=1e-5)
 
 
 @pytest.mark.parametrize('dof,rslm,plus', [(6, False, True), (4, True, False), (4, True, True)])

@@ -11,7 +11,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import epropnp_oracle as orc
-from helpers import make_layer_objects, pack_noise
+from helpers import make_layer_objects, pack_noise, vary_cameras
 
 
 def _free_port():
@@ -67,6 +67,55 @@ def _worker(rank, world, port, dof, ret):
         ret[rank] = bool(ok)
     finally:
         dist.destroy_process_group()
+
+
+def _worker_cameras(rank, world, port, dof, ret):
+    """every object on its own camera and bounds ('per_object'): the rank's shard of cam_mats / lb / ub, cut by
+    sharding.shard_objects like the correspondences, must be its objects' rows -- and the gathered result the single-process one"""
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    try:
+        import conftest
+        from epropnp import functional as F, sharding
+        import install as emu
+        emu.install(conftest._emu_lib())
+        B, N, S, K = 5, 48, 32, 2          # 5 objects over 2 ranks: uneven tail
+        prob = vary_cameras(orc.make_problem(B, N, dof, seed=40, bounds='tight' if dof == 4 else None), 'per_object', seed=42)
+        noise = pack_noise(orc.make_noise(B, S, K, dof, seed=41), dof)
+        lo, hi = sharding.shard_range(B)
+        keys = [k for k, v in prob.items() if isinstance(v, torch.Tensor) and v.dim() > 0 and v.shape[0] == B]
+        local = dict(zip(keys, sharding.shard_objects([prob[k] for k in keys], B)))
+        ok = all(torch.equal(local[k], prob[k][lo:hi]) for k in keys) and local['cam_mats'].shape == (hi - lo, 3, 3)
+        pose_l, logw_l = _run_shard(local, noise[lo:hi], dof, S, K, 0, hi - lo)
+        # what the kernels were handed: the contiguous views PnPProblem materialises from the shard
+        p, cam, cf = make_layer_objects(local, 'cpu')
+        hp = F.PnPProblem(p['x3d'], p['x2d'], p['w2d'], cam, cf, dof)
+        ok = ok and torch.equal(hp.cam, prob['cam_mats'][lo:hi]) and hp.cam.is_contiguous()
+        if 'lb' in prob:
+            ok = ok and torch.equal(hp.lb, prob['lb'][lo:hi]) and torch.equal(hp.ub, prob['ub'][lo:hi])
+        pose = sharding.gather_objects(pose_l, B, obj_dim=0)
+        logw = sharding.gather_objects(logw_l, B, obj_dim=1)
+        pose_full, logw_full = _run_shard(prob, noise, dof, S, K, 0, B)
+        ok = ok and pose.shape == (B, pose_full.shape[1]) and logw.shape == (S, B)
+        ok = ok and (pose - pose_full).abs().max().item() < 1e-6 and (logw - logw_full).abs().max().item() < 1e-5
+        # and the result is the cameras' own: with every object on object 0's camera the poses move
+        same_cam = dict(prob, cam_mats=prob['cam_mats'][:1].expand(B, 3, 3).contiguous())
+        ok = ok and (_run_shard(same_cam, noise, dof, S, K, 0, B)[0] - pose_full)[1:].abs().amax(1).min().item() > 1e-3
+        ret[rank] = bool(ok)
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize('dof', [6, 4])
+def test_object_sharding_per_object_cameras_gloo(dof):
+    import conftest
+    conftest._emu_lib()     # build once in the parent
+    world = 2
+    with mp.Manager() as mgr:
+        ret = mgr.dict()
+        mp.spawn(_worker_cameras, args=(world, _free_port(), dof, ret), nprocs=world, join=True)
+        assert dict(ret) == {0: True, 1: True}
 
 
 @pytest.mark.parametrize('dof', [6, 4])
