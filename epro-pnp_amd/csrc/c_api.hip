@@ -270,6 +270,46 @@ int epropnp_box_overlap_segmented(const float* boxes_a, int32_t num_a, const flo
                                            num_tiles, out, num_out, (hipStream_t)stream);
 }
 
+size_t epropnp_kitti_match_scratch_bytes(int32_t num_dt, int32_t num_cases) { return pnp::kitti_match_scratch_bytes(num_dt, num_cases); }
+
+// eval.py:166-284 with compute_fp=False, every case and image
+int epropnp_kitti_match(const void* overlaps, int32_t overlaps_fp64, int64_t num_overlaps, const int32_t* gt_offsets,
+                        const int32_t* dt_offsets, const int64_t* block_offsets, int32_t num_images, const double* dt_data,
+                        int32_t num_gt, int32_t num_dt, const int8_t* ignored_gt, const int8_t* ignored_det, const double* min_overlap,
+                        int32_t num_cases, void* scratch, size_t scratch_bytes, double* tp_scores, int32_t* tp_count, int8_t* gt_state,
+                        void* stream) {
+  pnp::StageScope prof_("kitti_match", (hipStream_t)stream);
+  return pnp::launch_kitti_match(overlaps, overlaps_fp64, (long long)num_overlaps, gt_offsets, dt_offsets, (const long long*)block_offsets,
+                                 num_images, dt_data, num_gt, num_dt, ignored_gt, ignored_det, min_overlap, num_cases, scratch,
+                                 scratch_bytes, tp_scores, tp_count, gt_state, (hipStream_t)stream);
+}
+
+// eval.py:12-30, every case
+int epropnp_kitti_thresholds(const double* sorted_scores, const int32_t* tp_count, const int32_t* num_valid_gt, int32_t num_gt,
+                             int32_t num_cases, double recall_step, double* thresholds, int32_t* thr_count, void* stream) {
+  pnp::StageScope prof_("kitti_thresholds", (hipStream_t)stream);
+  return pnp::launch_kitti_thresholds(sorted_scores, tp_count, num_valid_gt, num_gt, num_cases, recall_step, thresholds, thr_count,
+                                      (hipStream_t)stream);
+}
+
+size_t epropnp_kitti_statistics_scratch_bytes(int32_t num_images, int32_t num_dt, int32_t num_cases, int32_t compute_aos) {
+  return pnp::kitti_statistics_scratch_bytes(num_images, num_dt, num_cases, compute_aos);
+}
+
+// eval.py:166-284 with compute_fp=True under every threshold, summed over the images as eval.py:296-343 does
+int epropnp_kitti_statistics(const void* overlaps, int32_t overlaps_fp64, int64_t num_overlaps, const int32_t* gt_offsets,
+                             const int32_t* dt_offsets, const int32_t* dc_offsets, const int64_t* block_offsets, int32_t num_images,
+                             const double* gt_data, const double* dt_data, const double* dc_boxes, int32_t num_gt, int32_t num_dt,
+                             int32_t num_dc, const int8_t* ignored_gt, const int8_t* ignored_det, const double* min_overlap,
+                             int32_t num_cases, const double* thresholds, const int32_t* thr_count, int32_t metric, int32_t compute_aos,
+                             void* scratch, size_t scratch_bytes, double* pr, double* tp_scores, void* stream) {
+  pnp::StageScope prof_("kitti_statistics", (hipStream_t)stream);
+  return pnp::launch_kitti_statistics(overlaps, overlaps_fp64, (long long)num_overlaps, gt_offsets, dt_offsets, dc_offsets,
+                                      (const long long*)block_offsets, num_images, gt_data, dt_data, dc_boxes, num_gt, num_dt, num_dc,
+                                      ignored_gt, ignored_det, min_overlap, num_cases, thresholds, thr_count, metric, compute_aos, scratch,
+                                      scratch_bytes, pr, tp_scores, (hipStream_t)stream);
+}
+
 size_t epropnp_orient_density_scratch_bytes(int32_t mc_samples, int32_t num_obj) {
   return pnp::orient_density_scratch_bytes(mc_samples, num_obj);
 }

@@ -301,6 +301,22 @@ int box_overlap_plan(const int32_t* counts_a, const int32_t* counts_b, int G, in
 int launch_box_overlap_segmented(const float* boxes_a, int M, const float* boxes_b, int N, int kind, int crit, int z_axis,
                                  float z_center, int rule, const int32_t* tiles, int num_tiles, float* out, long long num_out,
                                  hipStream_t st);
+// kitti_eval_kernels.hip: the KITTI AP evaluation behind the overlap blocks (epropnp_kitti_match, _thresholds, _statistics): a count
+// fill and one launch for the matching pass, one launch for the thresholds, a count fill and two launches (per image, then the
+// fixed-order reduce) for the PR sums -- the same number whatever the images and cases
+int launch_kitti_match(const void* overlaps, int ov64, long long num_ov, const int32_t* gt_off, const int32_t* dt_off,
+                       const long long* blk_off, int I, const double* dt_data, int G, int D, const int8_t* ign_gt, const int8_t* ign_dt,
+                       const double* min_ov, int C, void* scratch, size_t scratch_bytes, double* tp_scores, int32_t* tp_count,
+                       int8_t* gt_state, hipStream_t st);
+int launch_kitti_thresholds(const double* sorted, const int32_t* tp_count, const int32_t* num_valid_gt, int G, int C, double recall_step,
+                            double* thresholds, int32_t* thr_count, hipStream_t st);
+int launch_kitti_statistics(const void* overlaps, int ov64, long long num_ov, const int32_t* gt_off, const int32_t* dt_off,
+                            const int32_t* dc_off, const long long* blk_off, int I, const double* gt_data, const double* dt_data,
+                            const double* dc_boxes, int G, int D, int Q, const int8_t* ign_gt, const int8_t* ign_dt, const double* min_ov,
+                            int C, const double* thresholds, const int32_t* thr_count, int metric, int compute_aos, void* scratch,
+                            size_t scratch_bytes, double* pr, double* tp_scores, hipStream_t st);
+size_t kitti_match_scratch_bytes(int D, int C);
+size_t kitti_statistics_scratch_bytes(int I, int D, int C, int compute_aos);
 // density_kernels.hip: density pictures of the weighted pose samples (epropnp_orient_density, epropnp_bev_density): one launch that
 // turns samples into weighted bins, one that sums them per 32 x 32 tile in LDS, box-filters and writes the picture
 int launch_orient_density(const float* pose, const float* logw, const float* pose_opt, int S, int B, int dof, int size, int kh,

@@ -106,6 +106,14 @@ def _declare(lib):
     lib.epropnp_box_overlap.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp]
     lib.epropnp_box_overlap_plan.argtypes = [vp, vp, i32, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.epropnp_box_overlap_segmented.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, i32, vp, i32, vp, C.c_int64, vp]
+    f64, sz = C.c_double, C.c_size_t
+    lib.epropnp_kitti_match.argtypes = [vp, i32, C.c_int64, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp]
+    lib.epropnp_kitti_thresholds.argtypes = [vp, vp, vp, i32, i32, f64, vp, vp, vp]
+    lib.epropnp_kitti_statistics.argtypes = [vp, i32, C.c_int64] + [vp] * 4 + [i32] + [vp] * 3 + [i32] * 3 + [vp] * 3 + [i32, vp, vp, i32, i32, vp, sz, vp, vp, vp]
+    lib.epropnp_kitti_match_scratch_bytes.argtypes = [i32, i32]
+    lib.epropnp_kitti_match_scratch_bytes.restype = sz
+    lib.epropnp_kitti_statistics_scratch_bytes.argtypes = [i32, i32, i32, i32]
+    lib.epropnp_kitti_statistics_scratch_bytes.restype = sz
     lib.epropnp_orient_density.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     lib.epropnp_bev_density.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
     for name in ('orient', 'bev'):
@@ -167,7 +175,7 @@ def _declare(lib):
                  'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms', 'orient_density',
                  'bev_density', 'deform_sample_forward', 'deform_sample_backward', 'roi_logsumexp_forward',
                  'roi_logsumexp_backward', 'roi_align_forward', 'roi_align_backward', 'box_overlap', 'box_overlap_plan',
-                 'box_overlap_segmented'):
+                 'box_overlap_segmented', 'kitti_match', 'kitti_thresholds', 'kitti_statistics'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -192,7 +200,9 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_orient_density', 'epropnp_orient_density_scratch_bytes', 'epropnp_bev_density',
            'epropnp_bev_density_scratch_bytes', 'epropnp_deform_sample_forward', 'epropnp_deform_sample_backward',
            'epropnp_roi_logsumexp_forward', 'epropnp_roi_logsumexp_backward', 'epropnp_roi_align_forward',
-           'epropnp_roi_align_backward', 'epropnp_box_overlap', 'epropnp_box_overlap_plan', 'epropnp_box_overlap_segmented')
+           'epropnp_roi_align_backward', 'epropnp_box_overlap', 'epropnp_box_overlap_plan', 'epropnp_box_overlap_segmented',
+           'epropnp_kitti_match', 'epropnp_kitti_match_scratch_bytes', 'epropnp_kitti_thresholds', 'epropnp_kitti_statistics',
+           'epropnp_kitti_statistics_scratch_bytes')
 
 
 def lib():

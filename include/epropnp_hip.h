@@ -416,6 +416,64 @@ int epropnp_box_overlap_segmented(const float* boxes_a, int32_t num_a, const flo
                                   const int32_t* tiles /* (num_tiles,6) device */, int32_t num_tiles, float* out /* (num_out,) */,
                                   int64_t num_out, void* stream);
 
+/* KITTI AP evaluation behind the per-image overlap blocks: greedy matching, recall thresholds and PR sums of the reference's
+ * core/evaluation/kitti_utils/eval.py for C "cases" (class x difficulty x minimum overlap) in one launch per stage.
+ * Layout, all DEVICE memory.  The I images are concatenated: gt_offsets, dt_offsets, dc_offsets (I+1,) int32 into the G ground
+ * truths, D detections and Q DontCare boxes, block_offsets (I+1,) int64 into the flat overlaps, whose block i is the row-major
+ * (detections of i, ground truths of i) matrix -- what epropnp_box_overlap_segmented writes with the detections as side A.  overlaps
+ * is float, or double with overlaps_fp64 != 0; every comparison is made in fp64 on the values as given.  gt_data (G,5): bbox x1 y1
+ * x2 y2, alpha.  dt_data (D,6): bbox, alpha, score.  dc_boxes (Q,4).  Per case: ignored_gt (C,G) and ignored_det (C,D) int8 in
+ * {-1, 0, 1} (clean_data's flags), min_overlap (C,) double, num_valid_gt (C,) int32.
+ * The offsets are memory: an image whose ranges leave [0,G], [0,D], [0,Q] or whose block leaves the overlaps is skipped -- nothing is
+ * read or written out of bounds, and such an image's slots of tp_scores / gt_state are the only output elements not written.
+ * Integer sums go through integer atomics; the fp64 similarity is added in a fixed order (chunks of consecutive images in image order, then
+ * the chunk sums in chunk order): a second call returns the same bits.  No allocation, no synchronisation.
+ *
+ * epropnp_kitti_match (compute_statistics_jit with compute_fp=False, eval.py:166-284, for every case and image): each ground truth
+ * that is not of another class takes, among the detections that are not of another class, not yet taken and overlap it by more than
+ * min_overlap, the one with the largest score > -1e7 (lowest index on a tie).  tp_scores (C,G) double: that score where the match is a
+ * true positive (neither side has ignore flag 1), -inf elsewhere.  tp_count (C,) int32: the true positives of each case.  gt_state
+ * (C,G) int8 or NULL: EPROPNP_KITTI_GT_* per ground truth.  scratch: epropnp_kitti_match_scratch_bytes(num_dt, num_cases) bytes.
+ *
+ * epropnp_kitti_thresholds (get_thresholds, eval.py:12-30): sorted_scores (C,G) is tp_scores with every row sorted descending;
+ * row c's first tp_count[c] entries are scanned with the reference's fp64 expressions ((i + 1) / num_gt, current_recall +=
+ * recall_step; recall_step = 1 / 40.0 for the 41 sample points).  thresholds (C,41) double, zeros beyond thr_count (C,) int32.
+ *
+ * epropnp_kitti_statistics (compute_statistics_jit with compute_fp=True summed by fused_compute_statistics, eval.py:296-343): for
+ * every case, image and threshold index below thr_count[c], which is read on the device.  pr (C,41,4) double: tp, fp, fn (exact
+ * integers) and the similarity sum of (1 + cos(gt_alpha - dt_alpha)) / 2 over the true positives (0 unless compute_aos); zeros beyond
+ * thr_count.  metric 0 takes detections inside DontCare boxes off fp.  tp_scores (C,41,G) or NULL: as epropnp_kitti_match's, per
+ * threshold; rows beyond thr_count are not written.  scratch: epropnp_kitti_statistics_scratch_bytes(num_images,
+ * num_dt, num_cases, compute_aos) bytes.
+ *
+ * num_cases == 0 launches nothing and follows no pointer.  EPROPNP_EINVAL: a negative count, more than 65535 cases, a metric outside
+ * 0 .. 2, a recall_step that is not positive, a NULL pointer to an array that has elements, scratch below the size query. */
+#define EPROPNP_KITTI_SAMPLE_PTS 41
+#define EPROPNP_KITTI_GT_SKIPPED (-1)      /* ignore flag -1: not visited */
+#define EPROPNP_KITTI_GT_UNMATCHED 0       /* ignore flag 1, no detection */
+#define EPROPNP_KITTI_GT_TRUE_POSITIVE 1
+#define EPROPNP_KITTI_GT_MISSED 2          /* ignore flag 0, no detection: a false negative */
+#define EPROPNP_KITTI_GT_IGNORED_MATCH 3   /* a detection was taken, and either side has ignore flag 1 */
+size_t epropnp_kitti_match_scratch_bytes(int32_t num_dt, int32_t num_cases);
+int epropnp_kitti_match(const void* overlaps, int32_t overlaps_fp64, int64_t num_overlaps, const int32_t* gt_offsets /* (I+1,) */,
+                        const int32_t* dt_offsets /* (I+1,) */, const int64_t* block_offsets /* (I+1,) */, int32_t num_images,
+                        const double* dt_data /* (D,6) */, int32_t num_gt, int32_t num_dt, const int8_t* ignored_gt /* (C,G) */,
+                        const int8_t* ignored_det /* (C,D) */, const double* min_overlap /* (C,) */, int32_t num_cases, void* scratch,
+                        size_t scratch_bytes, double* tp_scores /* (C,G) */, int32_t* tp_count /* (C,) */,
+                        int8_t* gt_state /* (C,G) or NULL */, void* stream);
+int epropnp_kitti_thresholds(const double* sorted_scores /* (C,G) */, const int32_t* tp_count /* (C,) */,
+                             const int32_t* num_valid_gt /* (C,) */, int32_t num_gt, int32_t num_cases, double recall_step,
+                             double* thresholds /* (C,41) */, int32_t* thr_count /* (C,) */, void* stream);
+size_t epropnp_kitti_statistics_scratch_bytes(int32_t num_images, int32_t num_dt, int32_t num_cases, int32_t compute_aos);
+int epropnp_kitti_statistics(const void* overlaps, int32_t overlaps_fp64, int64_t num_overlaps, const int32_t* gt_offsets,
+                             const int32_t* dt_offsets, const int32_t* dc_offsets, const int64_t* block_offsets, int32_t num_images,
+                             const double* gt_data /* (G,5) */, const double* dt_data /* (D,6) */, const double* dc_boxes /* (Q,4) */,
+                             int32_t num_gt, int32_t num_dt, int32_t num_dc, const int8_t* ignored_gt, const int8_t* ignored_det,
+                             const double* min_overlap, int32_t num_cases, const double* thresholds /* (C,41) */,
+                             const int32_t* thr_count /* (C,) */, int32_t metric, int32_t compute_aos, void* scratch,
+                             size_t scratch_bytes, double* pr /* (C,41,4) */, double* tp_scores /* (C,41,G) or NULL */,
+                             void* stream);
+
 /* Density pictures of the posterior, the weighted pose samples (S,B,P) + log-weights (S,B).  Both entries are one primitive -- a list
  * of weighted points (canvas, plane, pixel, weight) summed into pixels, then a zero-padded box sum of odd size -- in two launches:
  * one workgroup per object turns its samples into weights and bins; one workgroup per (canvas, 32 x 32 pixel tile) sums the points
@@ -476,7 +534,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "box_overlap", "box_overlap_segmented", "orient_density", "bev_density") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "box_overlap", "box_overlap_segmented", "orient_density", "bev_density", "kitti_match", "kitti_thresholds", "kitti_statistics") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
