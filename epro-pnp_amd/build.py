@@ -36,7 +36,7 @@ ERRATUM_FILES = tuple(SOURCES)
 # plain `hipcc -c` on a unit without swaps: tests/test_build_path.py).  Another toolchain: run that test, then add it here or set
 # EPROPNP_ALLOW_LLVM=<major>.
 VERIFIED_LLVM_MAJORS = (22,)
-HEADERS = ['pnp_math.h', 'wave_ops.h', 'pnp_sweep.h', 'pnp_host.h', 'dispatch.h', 'amis_common.h', 'lm_core.h', 'tuning.h']
+HEADERS = ['pnp_math.h', 'wave_ops.h', 'pnp_sweep.h', 'pnp_host.h', 'dispatch.h', 'amis_common.h', 'lm_core.h', 'tuning.h', 'amis_backward_sweep.inc']
 
 
 def _stale(target, deps):

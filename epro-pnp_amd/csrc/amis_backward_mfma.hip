@@ -60,7 +60,16 @@ constexpr int bwd_min_waves() { return (NPT <= 2) ? PNP_BWD_MINW : PNP_BWD_MINW4
 // Layout: qtab[pose][k] = {w0 of the x, y, z row | a3 of the x and y rows as two halves}, ztab[pose][k] = a3 of the z row (16 bits):
 // 18 dwords per pose next to the 15 of the fp32 table, whose K R rows the back-projection still reads (its K t slots are then dead).
 // Storing (a3, a3) as a word would take 24: 89.8 KB per workgroup at C2, where two workgroups per CU leave 80.
-template <int DOF, bool BOUNDS, int NPT, bool BF16 = false, bool DCOST = false, bool PRESPLIT = false>
+// ZFREE: a second body of the sweep without the depth clamp, taken for an object whose every table pose keeps every point in front of
+// z_min -- five of the 38 wave-level instructions per two pairs (two v_max_i32 in front of the reciprocals, then two clamped fmas and a
+// packed multiply for the 0/1 front factor) that return their input and multiply by 1 there.  The choice is per OBJECT and costs no
+// pass, barrier or branch of its own inside a loop: Rmax = max |x3d| (two points per thread at N = 512) rides through the block
+// reduction of amax; the table build, which holds (K R | K t) of its pose anyway, evaluates depth_clamp_clear (pnp_math.h: the bound,
+// its slack and why the bits are the same) and a thread whose pose fails clears an LDS word (red[kClearWord]) that the barrier behind
+// the build publishes; one scalar branch in front of the chunk loop picks the body.  Outputs are the clamped body's bits for every
+// input, NaN and inf included (those fail the bound).  Launched only where plan_amis_backward says it can pay; EPROPNP_TUNE=zfree=0 | 1.
+constexpr int kClearWord = 72;      // of red[80]: behind the compaction's 65 lane counts, beyond what the block reductions use
+template <int DOF, bool BOUNDS, int NPT, bool BF16 = false, bool DCOST = false, bool PRESPLIT = false, bool ZFREE = false>
 __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) void amis_backward_mfma_kernel(Problem p, const float* __restrict__ pose_samples,
                                                                      const float* __restrict__ g_logw, int S,
                                                                      const float* __restrict__ pose_init,
@@ -148,7 +157,18 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
     wraw[m] = w;
     if (m < S) amax = fmaxf(amax, fabsf(w));
   }
-  amax = block_max(amax, red);          // (barriers inside: wraw is visible to every wave afterwards)
+  float Rmax = 0.f;
+  if constexpr (ZFREE) {      // the object's largest |x3d|, for the table build's bound: one more value through the reduction of amax
+    float r2 = 0.f;
+    for (int n = tid; n < p.N; n += T) {
+      const float* x = p.x3d + ((size_t)b * p.N + n) * 3;
+      r2 = fmaxf(r2, depth_r2(x[0], x[1], x[2]));
+    }
+    block_max2(amax, r2, red);
+    Rmax = depth_rmax_up(r2);
+  } else {
+    amax = block_max(amax, red);          // (barriers inside: wraw is visible to every wave afterwards)
+  }
   __syncthreads();
   PNP_PHASE(0);
   const float askip = mass_drop_threshold([&](int m) { return fabsf(wraw[m]); }, S, amax, drop_eps, hist);
@@ -173,6 +193,7 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
     for (int m = m0; m < m1; ++m)
       if (wraw[m] != 0.f) idx[off++] = m;
     if (lane == 0) lcnt[64] = total;
+    if (ZFREE && lane == 0) lcnt[kClearWord] = 1;      // "every pose of the table clears z_min" until a build thread says otherwise
   }
   __syncthreads();
   PNP_PHASE(2);
@@ -205,9 +226,15 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
         comp[4 * r + 3] = Kt[r];
       }
       wtab[c] = wraw[m];
-    } else {     // padding of the last tile: a harmless pose (depth 1) with zero weight
+      // ZFREE: a pose that may put a point behind z_min clears the word.  Every such thread stores the same 0 -- a benign race --
+      // and the barrier behind the build publishes it.
+      if constexpr (ZFREE) {
+        if (!depth_clamp_clear(KR[6], KR[7], KR[8], Kt[2], Rmax, p.z_min)) reinterpret_cast<int*>(red)[kClearWord] = 0;
+      }
+    } else {     // padding of the last tile: a harmless pose (depth 1; ZFREE: a depth that passes the bound for any z_min) with zero weight
+      const float pad_z = ZFREE ? fmaxf(1.f, 2.f * p.z_min) : 1.f;
 #pragma unroll
-      for (int k = 0; k < 12; ++k) comp[k] = (k == 11) ? 1.f : 0.f;
+      for (int k = 0; k < 12; ++k) comp[k] = (k == 11) ? pad_z : 0.f;
       wtab[c] = 0.f;
     }
 #pragma unroll
@@ -227,6 +254,8 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
     }
   }
   __syncthreads();
+  // workgroup-uniform, read before the block sum below reuses `red`
+  const bool clear = ZFREE && __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(red)[kClearWord]) != 0;
   float Cb = 0.f;
   if (DCOST) {      // one block sum in a fixed order (wave_ops.h); the total is wave-uniform: kept in a scalar register across the sweep
     block_sum<1>(csum, red);
@@ -237,191 +266,23 @@ __global__ __launch_bounds__(512, (bwd_min_waves<DOF, BOUNDS, NPT, BF16>())) voi
   const int col = lane & 15, kk = lane >> 4, g4 = kk * 4;
   float gd = 0.f;
   const int chunk_pts = W * NPT * 16;
-  for (int c0 = part * chunk_pts; c0 < p.N; c0 += nsplit * chunk_pts) {
-    // this wave's point tiles q = wv + W * i of the chunk; lane = (point column, k)
-    typename Proj::T rB[NPT];
-    float4 rW[NPT];
-    // per resident tile: the four sums behind d/du, d/dw and the back-projected gradient, as PAIRS over the lane's poses (0, 2 | 1, 3):
-    // folded once per chunk (below).  14 VGPRs per tile instead of 7 -- the two-tile instantiation has them to spare below the
-    // three-waves-per-SIMD budget of 168, and they save 3.5 wave-level instructions per pair (8 scalar fmacs -> 4 packed fmas per two
-    // pairs, no folding adds per pose tile).
-    f32x2 A1x[NPT], A1y[NPT], A2x[NPT], A2y[NPT];
-    f32x2 gXv[NPT], gYv[NPT], gZv[NPT];
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      const Point q = load_point(p, b, c0 + (wv + W * i) * 16 + col);      // zero weight beyond N
-      rB[i] = Proj::b((kk == 0) ? q.X : (kk == 1) ? q.Y : (kk == 2) ? q.Z : 1.0f);
-      const float wu = q.wu * hs.inv_delta, wv = q.wv * hs.inv_delta;
-      rW[i] = make_float4(wu, -q.u * wu, wv, -q.v * wv);      // (w_u, c_u | w_v, c_v): the factors in the low halves of their pairs
-      A1x[i] = A1y[i] = A2x[i] = A2y[i] = f32x2{0.f, 0.f};
-      gXv[i] = gYv[i] = gZv[i] = f32x2{0.f, 0.f};
+  // The sweep over the chunks, once with the depth clamp and -- ZFREE -- once without: `clear` chooses per object, outside every loop.
+  // CLAMP = false drops clamp_below in front of the reciprocal (which then reads the matrix instruction's result directly) and the
+  // 0/1 front factor of ghz2: where depth_clamp_clear (pnp_math.h) holds for every pose of the table both are the identity, bit for bit.
+  // It is ONE text, amis_backward_sweep.inc, included once per body with CLAMP set -- not a function or a lambda: with the chunk loop
+  // in a lambda (by reference or by value, inlined by force or not) the instantiations without a second body no longer compiled to
+  // the code they had (two VGPRs more at four tiles, another schedule).  As it is, their device code is unchanged.
+  if constexpr (ZFREE) {
+    if (clear) {
+      constexpr bool CLAMP = false;
+#include "amis_backward_sweep.inc"
+    } else {
+      constexpr bool CLAMP = true;
+#include "amis_backward_sweep.inc"
     }
-    f32x2 gsat2 = {0.f, 0.f};   // sum_pairs a_j min(|r|^2, 1): the second term of d/d delta (below), poses (0, 2) | (1, 3) of the lanes
-    const floatx4 zero = {0.f, 0.f, 0.f, 0.f};
-    const f32x2 tiny2 = {tiny_v, tiny_v};
-    // The pair loop on 2-VECTORS: a lane's four poses of a tile are two register pairs (MFMA result elements 0, 1 | 2, 3; the pose
-    // table above delivers every per-pose operand as such pairs), and every multiply / fma below is ONE v_pk_*_f32 for two pairs.  Packed
-    // fp32 issues at half the rate of the scalar form, so the arithmetic throughput is the same -- but this loop is not bound by that:
-    // it is bound by how often a wave gets to issue (profiles/r06_bwd_probe.txt: 10 % fewer instructions changed nothing, a fourth wave
-    // per SIMD gave 6 %), and the packed form needs ~40 % fewer issues per pair.  Shapes: plain operands, broadcasts from the LOW half of
-    // a pair (op_sel_hi) and negations only -- never the (lo, hi) source selection of profiles/r05_pk_opsel_erratum.txt; the build's
-    // assembly gate (tools/pk_opsel_fix.py --audit) and tests/test_erratum_gpu.py hold that line.
-    // (Round 6 also tried a second loop body without the depth clamp for pose tiles whose depths all clear z_min -- three instructions
-    // per pair less -- chosen per tile by a bound on |X|: no gain at C2 for the reason above, and 10-20 us more per launch at the
-    // few-object shapes for the bound's extra pass and barriers; removed.)
-    for (int t = 0; t < ntile; ++t) {
-      typename Proj::T ax, ay, az;
-      if constexpr (PRESPLIT) {      // A operands rebuilt from the stored words of pose (tile t, row col), k-slice kk
-        const u32x4 q = qtab[(t * 16 + col) * 4 + kk];
-        const unsigned z = ztab[(t * 16 + col) * 4 + kk];
-        ax = bf16_a_from_words(q[0], bf16_dup_lo(q[3]));
-        ay = bf16_a_from_words(q[1], bf16_dup_hi(q[3]));
-        az = bf16_a_from_words(q[2], bf16_dup_lo(z));
-      } else {
-        const float* grp = ptab + (t * 4 + (col >> 2)) * 48 + (col & 3);
-        ax = Proj::a(grp[kk * 4]); ay = Proj::a(grp[(4 + kk) * 4]); az = Proj::a(grp[(8 + kk) * 4]);
-      }
-      const float4 aw4 = *reinterpret_cast<const float4*>(wtab + t * 16 + g4);
-      // this lane's 4 poses: rows of K R (the back-projection), one float4 = one component of the four poses
-      const float4* rows = reinterpret_cast<const float4*>(ptab + (t * 4 + kk) * 48);
-      const float4 kxx = rows[0], kxy = rows[1], kxz = rows[2], kyx = rows[4], kyy = rows[5], kyz = rows[6], kzx = rows[8], kzy = rows[9],
-                   kzz = rows[10];
-      // Four resident tiles (two waves per SIMD, registers to spare): a software pipeline over the tiles -- tile i + 1's three
-      // projections are issued in front of tile i's pair work, so that no wave waits out an MFMA's result latency in s_nops (29 -> 1
-      // per pose tile).  With one or two tiles the compiler's own placement is the better one (the fence costs it its freedom).
-      constexpr bool kPipe = (NPT == 4);
-      floatx4 hxn = zero, hyn = zero, hzn = zero;
-      if (kPipe) {
-        hxn = Proj::mma(ax, rB[0], zero); hyn = Proj::mma(ay, rB[0], zero); hzn = Proj::mma(az, rB[0], zero);
-      }
-#pragma unroll
-      for (int i = 0; i < NPT; ++i) {
-        floatx4 hx, hy, hz;
-        if (kPipe) {
-          hx = hxn; hy = hyn; hz = hzn;
-          if (i + 1 < NPT) {
-            hxn = Proj::mma(ax, rB[i + 1], zero);
-            hyn = Proj::mma(ay, rB[i + 1], zero);
-            hzn = Proj::mma(az, rB[i + 1], zero);
-            sched_fence();
-          }
-        } else {
-          hx = Proj::mma(ax, rB[i], zero);
-          hy = Proj::mma(ay, rB[i], zero);
-          hz = Proj::mma(az, rB[i], zero);
-        }
-        const float4 w4 = rW[i];
-        const f32x2 wu2 = {w4.x, w4.x}, cu2 = {w4.y, w4.y}, wv2 = {w4.z, w4.z}, cv2 = {w4.w, w4.w};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const f32x2 hx2 = {hx[2 * h], hx[2 * h + 1]}, hy2 = {hy[2 * h], hy[2 * h + 1]};
-          const float hz0 = hz[2 * h], hz1 = hz[2 * h + 1];
-          const f32x2 aw2 = h ? f32x2{aw4.z, aw4.w} : f32x2{aw4.x, aw4.y};
-          const f32x2 rz2 = {fast_rcp(clamp_below(hz0, zmin_v)), fast_rcp(clamp_below(hz1, zmin_v))};
-          f32x2 rx2, ry2, ghx2, ghy2, ghz2;
-          // Huber weight min(1, delta / rho) = min(1, rs) straight from the reciprocal norm (rho * rs = 1): ONE clamped multiply where
-          // rho, min(rho, 1) and their product with rs took three.
-          // d huber / d delta = max(rho - delta, 0) (/ delta) = coef |r|^2 - a min(|r|^2, 1) (residuals in units of delta; outlier:
-          // a rho - a, inlier: a rho^2 - a rho^2 = 0): the first term is what A2x + A2y accumulate anyway, the second costs one clamped
-          // multiply per pair and a packed fma (`gsat2`) where rho, rho (1 - c1) and the accumulation took three instructions per pair.
-          f32x2 coef2, crx2, cry2;
-          if (!BOUNDS) {
-            // no projection clamp: the weight goes into the reciprocal depth once (w / z), which serves the residual and the
-            // gradient w.r.t. (h_x, h_y) -- one multiply per pair less than projecting first
-            const f32x2 wrx2 = rz2 * wu2, wry2 = rz2 * wv2;
-            rx2 = fma2(hx2, wrx2, cu2);
-            ry2 = fma2(hy2, wry2, cv2);
-            const f32x2 s22 = fma2(rx2, rx2, fma2(ry2, ry2, tiny2));      // |r|^2 + 1e-30: one v_max less per pair than clamping
-            const f32x2 c12 = {sat_mul(fast_rsqrt(s22[0]), one_v), sat_mul(fast_rsqrt(s22[1]), one_v)};
-            coef2 = aw2 * c12;
-            if (!DCOST) gsat2 = fma2(aw2, f32x2{sat_mul(s22[0], one_v), sat_mul(s22[1], one_v)}, gsat2);
-            crx2 = coef2 * rx2;
-            cry2 = coef2 * ry2;
-            ghx2 = crx2 * wrx2;
-            ghy2 = cry2 * wry2;
-            ghz2 = -rz2 * fma2(ghx2, hx2, ghy2 * hy2);                      // = -(ghx p_x + ghy p_y)
-          } else {
-            const f32x2 ppx2 = hx2 * rz2, ppy2 = hy2 * rz2;                 // un-clamped projection
-            const f32x2 px2 = {clamp_lu(ppx2[0], bd.lbx, bd.ubx), clamp_lu(ppx2[1], bd.lbx, bd.ubx)};
-            const f32x2 py2 = {clamp_lu(ppy2[0], bd.lby, bd.uby), clamp_lu(ppy2[1], bd.lby, bd.uby)};
-            rx2 = fma2(px2, wu2, cu2);
-            ry2 = fma2(py2, wv2, cv2);
-            const f32x2 s22 = fma2(rx2, rx2, fma2(ry2, ry2, tiny2));
-            const f32x2 c12 = {sat_mul(fast_rsqrt(s22[0]), one_v), sat_mul(fast_rsqrt(s22[1]), one_v)};
-            coef2 = aw2 * c12;
-            if (!DCOST) gsat2 = fma2(aw2, f32x2{sat_mul(s22[0], one_v), sat_mul(s22[1], one_v)}, gsat2);
-            crx2 = coef2 * rx2;
-            cry2 = coef2 * ry2;
-            f32x2 gpx2 = crx2 * wu2, gpy2 = cry2 * wv2;
-            // the clamp passes no gradient where it is active: inside [lb, ub] <=> clamp(x) == x
-            gpx2 = f32x2{(px2[0] == ppx2[0]) ? gpx2[0] : 0.f, (px2[1] == ppx2[1]) ? gpx2[1] : 0.f};
-            gpy2 = f32x2{(py2[0] == ppy2[0]) ? gpy2[0] : 0.f, (py2[1] == ppy2[1]) ? gpy2[1] : 0.f};
-            ghx2 = gpx2 * rz2;
-            ghy2 = gpy2 * rz2;
-            ghz2 = fma2(-ghx2, ppx2, -(ghy2 * ppy2));
-          }
-          // "in front of the depth clamp" as a 0/1 factor from ONE full-rate instruction per pair (front_scale above)
-          ghz2 = ghz2 * f32x2{sat_fma(hz0, front_scale, front_off), sat_fma(hz1, front_scale, front_off)};
-          // d/dw = crx * (px - u) = crx * rx / w and d/du = -crx * w: the per-point factors are applied once at the end
-          A2x[i] = fma2(crx2, rx2, A2x[i]);
-          A2y[i] = fma2(cry2, ry2, A2y[i]);
-          A1x[i] = fma2(coef2, rx2, A1x[i]);
-          A1y[i] = fma2(coef2, ry2, A1y[i]);
-          const f32x2 kxx2 = h ? f32x2{kxx.z, kxx.w} : f32x2{kxx.x, kxx.y}, kyx2 = h ? f32x2{kyx.z, kyx.w} : f32x2{kyx.x, kyx.y},
-                      kzx2 = h ? f32x2{kzx.z, kzx.w} : f32x2{kzx.x, kzx.y};
-          const f32x2 kxy2 = h ? f32x2{kxy.z, kxy.w} : f32x2{kxy.x, kxy.y}, kyy2 = h ? f32x2{kyy.z, kyy.w} : f32x2{kyy.x, kyy.y},
-                      kzy2 = h ? f32x2{kzy.z, kzy.w} : f32x2{kzy.x, kzy.y};
-          const f32x2 kxz2 = h ? f32x2{kxz.z, kxz.w} : f32x2{kxz.x, kxz.y}, kyz2 = h ? f32x2{kyz.z, kyz.w} : f32x2{kyz.x, kyz.y},
-                      kzz2 = h ? f32x2{kzz.z, kzz.w} : f32x2{kzz.x, kzz.y};
-          gXv[i] = fma2(kxx2, ghx2, fma2(kyx2, ghy2, fma2(kzx2, ghz2, gXv[i])));
-          gYv[i] = fma2(kxy2, ghx2, fma2(kyy2, ghy2, fma2(kzy2, ghz2, gYv[i])));
-          gZv[i] = fma2(kxz2, ghx2, fma2(kyz2, ghy2, fma2(kzz2, ghz2, gZv[i])));
-        }
-      }
-    }
-    const float gsat = gsat2[0] + gsat2[1];
-    {   // d/d delta of this chunk: sum_pairs coef |r|^2 (= the sums behind d/dw, before their per-point factors) - sum_pairs a min(|r|^2, 1)
-        // (DCOST: 2 C_b - sum_pairs coef |r|^2, the object's C_b added once behind the chunk loop)
-      float a2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < NPT; ++i) a2 += (A2x[i][0] + A2x[i][1]) + (A2y[i][0] + A2y[i][1]);
-      gd += DCOST ? -a2 : a2 - gsat;
-    }
-    // ---- outputs of this chunk: sums over the 4 pose groups of a point via MFMAs against indicator columns ----
-    // The lane geometry is re-derived here behind an opaque copy of the lane index: as invariants of the chunk loop the four
-    // indicator columns and the three 64-bit output addresses were hoisted in front of it and stayed live across the pose-tile
-    // loop -- 10 VGPRs, which cost the bf16 instantiation 7 spilled dwords per lane (33 MB of scratch traffic per launch at C2).
-    const int laneE = (int)f32_bits(to_vgpr(bits_f32((unsigned)lane)));
-    const int colE = laneE & 15, g4E = (laneE >> 4) * 4;
-    const float ind0 = (colE == 0) ? 1.f : 0.f, ind1 = (colE == 1) ? 1.f : 0.f, ind2 = (colE == 2) ? 1.f : 0.f,
-                ind3 = (colE == 3) ? 1.f : 0.f;
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      floatx4 D1 = zero;
-      D1 = mfma_16x16x4((gXv[i][0] + gXv[i][1]) * hs.delta_sq, ind0, D1);
-      D1 = mfma_16x16x4((gYv[i][0] + gYv[i][1]) * hs.delta_sq, ind1, D1);
-      D1 = mfma_16x16x4((gZv[i][0] + gZv[i][1]) * hs.delta_sq, ind2, D1);
-      const float4 w4 = rW[i];
-      floatx4 D2 = zero;
-      const float a1x = A1x[i][0] + A1x[i][1], a1y = A1y[i][0] + A1y[i][1], a2x = A2x[i][0] + A2x[i][1], a2y = A2y[i][0] + A2y[i][1];
-      D2 = mfma_16x16x4(-w4.x * a1x * hs.delta_sq, ind0, D2);                               // d/du
-      D2 = mfma_16x16x4(-w4.z * a1y * hs.delta_sq, ind1, D2);                               // d/dv
-      D2 = mfma_16x16x4((w4.x != 0.f) ? a2x * hs.delta / w4.x : 0.f, ind2, D2);             // d/dwu
-      D2 = mfma_16x16x4((w4.z != 0.f) ? a2y * hs.delta / w4.z : 0.f, ind3, D2);             // d/dwv
-      const int nb = c0 + (wv + W * i) * 16 + g4E;    // D rows: points nb + r; column = lane & 15
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = nb + r;
-        if (n < p.N) {
-          const size_t o = (size_t)b * p.N + n;
-          if (colE < 3) gx3d[o * 3 + colE] = D1[r];
-          if (colE < 2) gx2d[o * 2 + colE] = D2[r];
-          else if (colE < 4) {
-            if (park) gwl[n * 2 + (colE - 2)] = D2[r]; else gw2d[o * 2 + (colE - 2)] = D2[r];
-          }
-        }
-      }
-    }
+  } else {
+    constexpr bool CLAMP = true;
+#include "amis_backward_sweep.inc"
   }
   PNP_PHASE(4);
   if (DCOST && part == 0 && tid == 0) gd += 2.0f * Cb;      // (split launch: the partials of the other parts stay partials)
@@ -460,7 +321,7 @@ static int dispatch_bwd_npt(int npt, F&& f) {
 struct BwdPlan {
   int waves, npt, P16, gw_rows;
   size_t smem;
-  bool bf16, presplit;
+  bool bf16, presplit, zfree;
 };
 
 // Which instantiation launch_amis_backward_mfma launches, and with what shape: a pure host function of the sizes, the tuning
@@ -516,6 +377,14 @@ static int plan_amis_backward(const epropnp_problem* prob, int mc_samples, bool 
     { int ov[1]; if (tune_ints("bwd_presplit", ov, 1) && ov[0] == 0) presplit = false; }
     if (presplit) smem = pre;
   }
+  // The sweep with a second, clamp-free body (kernel comment: ZFREE) exists for the pre-split instantiations of the unsplit launch.
+  // It is taken where it was measured to pay (profiles/zfree_bench.txt): 6-DoF without a projection clamp, four resident tiles, and a
+  // grid that fills the device at the two workgroups per CU of that shape -- with fewer objects the per-object set-up (the pass for
+  // Rmax) is not hidden behind other workgroups' sweeps.  EPROPNP_TUNE=zfree=0 never takes it (the A/B switch, the tests' reference),
+  // zfree=1 takes it wherever it exists, whatever the grid: the outputs are the same bits either way.
+  bool zfree = presplit && nsplit == 1 && prob->dof == 6 && !has_bounds(prob) && npt == 4 && B >= 2 * device_cu_count();
+  { int ov[1]; if (tune_ints("zfree", ov, 1)) zfree = presplit && nsplit == 1 && ov[0] != 0; }
+  out->zfree = zfree;
   out->waves = waves; out->npt = npt; out->P16 = P16; out->gw_rows = gw_rows; out->smem = smem; out->bf16 = bf16; out->presplit = presplit;
   return 0;
 }
@@ -558,6 +427,9 @@ int launch_amis_backward_mfma(const epropnp_problem* prob, const float* pose_sam
     return dispatch_bwd_npt(npt, [&](auto NPT) -> int {
       constexpr int kDof = decltype(DOF)::value, kNpt = decltype(NPT)::value;
       constexpr bool kBnd = decltype(BND)::value;
+      if (plan.zfree)
+        return dcost ? launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true, true, true, true>)
+                     : launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true, false, true, true>);
       if (plan.presplit)
         return dcost ? launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true, true, true>)
                      : launch(amis_backward_mfma_kernel<kDof, kBnd, kNpt, true, false, true>);

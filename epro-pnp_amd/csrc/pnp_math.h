@@ -246,6 +246,48 @@ PNP_FN float sweep_cost(const SweepPoint& p, const float (&KR)[9], const float (
   return m * fmaf(-0.5f, m, rho);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// "the depth clamp is inactive": a bound that lets an AMIS sweep drop max(h_z, z_min) for a whole object
+// ---------------------------------------------------------------------------------------------------
+// Rmax = max_n |x3d_n| from the largest squared norm, rounded UP.  The squared norm (three fp32 operations, fused or not) is within
+// 3 * 2^-24 relative of the true one, the square root halves that and adds its own 2^-24 (1 ulp for the hardware approximation):
+// the factor 1 + 2^-12 covers it more than a thousand times over.  depth_r2 turns a NaN squared norm (a NaN coordinate) into +inf,
+// which a maximum keeps where fmaxf would drop the NaN; an overflowed norm is +inf as well.  Either way Rmax = +inf: never clear.
+PNP_FN float depth_r2(float X, float Y, float Z) {
+  const float r2 = fmaf(X, X, fmaf(Y, Y, Z * Z));
+  return (r2 < INFINITY) ? r2 : INFINITY;
+}
+PNP_FN float depth_rmax_up(float r2max) { return sqrtf(r2max) * (1.0f + 0x1p-12f); }
+
+// True only if  h_z = kz . (X, Y, Z) + ktz >= z_min  is guaranteed for EVERY point with |(X, Y, Z)| <= Rmax, as the projection
+// MFMAs compute it (fp32 16x16x4 and the bf16x3 split alike); (kz | ktz) is the z row of (K R | K t).
+//   * Exact arithmetic, Cauchy-Schwarz:  h_z >= ktz - |kz| Rmax, and the sum of the four terms' magnitudes is
+//     M = |ktz| + |kz . x|_1 <= |ktz| + |kz| Rmax.
+//   * The matrix instruction: |computed - exact| <= e M with e = 1.4e-7 measured for the split (profiles/r02_tune_fwd_bf16_split.txt;
+//     the fp32 instruction's four products and three sums stay below 4 * 2^-24 = 2.4e-7).
+//   * This function's own fp32 arithmetic: |kz| from three squares, two sums and a square root, the product with Rmax, two
+//     subtractions -- each within 2^-24 relative of numbers no larger than M, below 8 * 2^-24 M = 4.8e-7 M in all.  Squares of
+//     components below 1e-19 underflow: 2^-60 is added to the norm, more than the norm of three such components.
+//   Slack: the product is inflated by 2^-8 and 2^-16 M is subtracted, i.e. at least 2^-16 M = 1.5e-5 M against (1.4e-7 + 4.8e-7) M of
+//   error: a factor of 24 over everything, of 109 over the projection's own error.
+//   * Written as !(lb >= ...) -> not clear: a NaN or inf row, a NaN or inf Rmax (inf - inf, 0 * inf) make lb NaN or -inf.
+// Where it says "clear", a sweep without the clamp produces the clamped sweep's bits:
+//   * clamp_below (amis_common.h) is an integer maximum of the bit patterns.  h_z >= lb >= 2^-30 > 0 is a positive non-NaN float;
+//     positive floats order like their bits, and a z_min <= 0 is the bit pattern of a non-positive integer (or of +0): the maximum is
+//     h_z itself whenever h_z >= z_min, for every sign of z_min.  (Without the floor of 2^-30 a h_z of -0 would pass z_min = 0 and come
+//     out of the integer maximum as +0.)
+//   * The backward's front factor is clamp(fma(h_z, 2^60, -z_lo 2^60), 0, 1) with z_lo the float next to z_min towards -1 (the
+//     product z_lo 2^60 is exact).  For z_min >= 2^-30: h_z - z_lo >= z_min - z_lo >= 2^-24 z_min >= 2^-54.  For a smaller z_min:
+//     z_lo < 2^-31 and h_z - z_lo > 2^-31.  Times 2^60 that is at least 2^6: the fma rounds a number >= 1 (or gives +inf), the factor
+//     is exactly 1.0f and multiplying by it is exact.  z_min is capped at 2^30 so that z_lo 2^60 stays finite (no inf - inf).
+PNP_FN bool depth_clamp_clear(float kzx, float kzy, float kzz, float ktz, float Rmax, float z_min) {
+  const float nrm = sqrtf(fmaf(kzx, kzx, fmaf(kzy, kzy, kzz * kzz))) + 0x1p-60f;
+  const float reach = nrm * Rmax;
+  const float lb = (ktz - reach * (1.0f + 0x1p-8f)) - 0x1p-16f * (fabsf(ktz) + reach);
+  if (!(lb >= fmaxf(z_min, 0x1p-30f))) return false;
+  return z_min <= 0x1p30f;
+}
+
 // Exact-form Huber (same expression as cost_fun.py:8-12) for the non-fast paths.
 PNP_FN float huber_exact(float rho, float delta) {
   return (rho <= delta) ? 0.5f * rho * rho : delta * rho - 0.5f * delta * delta;

@@ -312,4 +312,25 @@ __device__ __forceinline__ float block_max(float x, float* scratch) {
   return m;
 }
 
+// Two maxima through the barriers of one: block_max of `a` and of `b`, in place.  `scratch` holds 2 * (blockDim.x / 64) floats.
+__device__ __forceinline__ void block_max2(float& a, float& b, float* scratch) {
+  const int nw = (int)(blockDim.x >> 6);
+  a = wave_max(a);
+  b = wave_max(b);
+  if (nw == 1) return;
+  if (lane_id() == 0) {
+    scratch[2 * wave_id()] = a;
+    scratch[2 * wave_id() + 1] = b;
+  }
+  __syncthreads();
+  float ma = scratch[0], mb = scratch[1];
+  for (int k = 1; k < nw; ++k) {
+    ma = fmaxf(ma, scratch[2 * k]);
+    mb = fmaxf(mb, scratch[2 * k + 1]);
+  }
+  __syncthreads();
+  a = ma;
+  b = mb;
+}
+
 }  // namespace pnp

@@ -73,6 +73,8 @@ VARIANTS = [
     ('default', {}),
     # the backward's pose rows split to bf16 on the fly by every wave of the sweep, instead of once while the pose table is built
     ('bwd_split_on_the_fly', {'EPROPNP_TUNE': 'bwd_presplit=0'}),
+    # the backward's sweep with the depth clamp for every object, instead of a clamp-free body for objects whose poses all clear z_min
+    ('bwd_depth_clamp_always', {'EPROPNP_TUNE': 'zfree=0'}),
     # the forward's per-tile weights in registers (168 VGPRs, three workgroups per CU at C2) instead of LDS (106, four)
     ('fwd_weights_in_registers', {'EPROPNP_TUNE': 'fwd_wlds=0'}),
 ]
