@@ -337,6 +337,30 @@ int epropnp_bev_density(const float* pose_samples, const float* logweights, cons
                                  width, scale, origin_x, origin_y, window, scratch, scratch_bytes, density, bins, (hipStream_t)stream);
 }
 
+size_t epropnp_volume_centers_scratch_bytes(int32_t num_obj, int32_t h_out, int32_t w_out) {
+  return pnp::volume_centers_scratch_bytes(num_obj, h_out, w_out);
+}
+
+// center_target.py:42-259 (VolumeCenter.get_centers_2d + post_proc, box mesh) without a render
+int epropnp_volume_centers(const float* bboxes_3d, const float* bboxes_2d_in, const int32_t* obj_offsets, const float* cam_intrinsic,
+                           const float* dense_x2d, const float* dense_mask, int32_t num_obj, int32_t num_img, int32_t h_out,
+                           int32_t w_out, int32_t h_rend, int32_t w_rend, int32_t output_stride, int32_t render_stride,
+                           int32_t faces_per_pixel, float z_clip, float min_box_size, int32_t get_bbox_2d, void* scratch,
+                           size_t scratch_bytes, float* centers_2d, float* bboxes_2d, uint8_t* valid, void* stream) {
+  pnp::StageScope prof_("volume_centers", (hipStream_t)stream);
+  return pnp::launch_volume_centers(bboxes_3d, bboxes_2d_in, obj_offsets, cam_intrinsic, dense_x2d, dense_mask, num_obj, num_img, h_out,
+                                    w_out, h_rend, w_rend, output_stride, render_stride, faces_per_pixel, z_clip, min_box_size,
+                                    get_bbox_2d, scratch, scratch_bytes, centers_2d, bboxes_2d, valid, (hipStream_t)stream);
+}
+
+int epropnp_box_thickness(const float* bboxes_3d, const int32_t* obj_offsets, const float* cam_intrinsic, int32_t num_obj,
+                          int32_t num_img, int32_t h_rend, int32_t w_rend, int32_t render_stride, int32_t faces_per_pixel, float z_clip,
+                          void* scratch, size_t scratch_bytes, float* thickness, uint8_t* valid, void* stream) {
+  pnp::StageScope prof_("box_thickness", (hipStream_t)stream);
+  return pnp::launch_box_thickness(bboxes_3d, obj_offsets, cam_intrinsic, num_obj, num_img, h_rend, w_rend, render_stride,
+                                   faces_per_pixel, z_clip, scratch, scratch_bytes, thickness, valid, (hipStream_t)stream);
+}
+
 int epropnp_deform_sample_forward(const float* query, const float* key, const float* value, const float* dense_x2d,
                                   const float* dense_mask, const float* sampling_location, const int64_t* obj_img_ind,
                                   int32_t num_obj, int32_t num_img, int32_t num_heads, int32_t num_points, int32_t head_dim,

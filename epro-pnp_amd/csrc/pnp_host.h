@@ -327,6 +327,15 @@ int launch_bev_density(const float* pose, const float* logw, const float* obj_we
                        float* density, int32_t* bins, hipStream_t st);
 size_t orient_density_scratch_bytes(int S, int B);
 size_t bev_density_scratch_bytes(int S, int B);
+// center_target_kernels.hip: the training step's centre targets (epropnp_volume_centers: the per-object table, the per-tile partials,
+// the fixed-order fp64 reduce -- three launches) and the render the fused pass never stores (epropnp_box_thickness: table + one launch)
+int launch_volume_centers(const float* boxes3d, const float* boxes2d_in, const int32_t* offsets, const float* cam, const float* x2d,
+                          const float* mask, int B, int G, int h, int w, int Hr, int Wr, int os, int rs, int K, float zc,
+                          float min_box, int want_box, void* scratch, size_t scratch_bytes, float* centers, float* boxes2d,
+                          uint8_t* valid, hipStream_t st);
+int launch_box_thickness(const float* boxes3d, const int32_t* offsets, const float* cam, int B, int G, int Hr, int Wr, int rs, int K,
+                         float zc, void* scratch, size_t scratch_bytes, float* thick, uint8_t* valid, hipStream_t st);
+size_t volume_centers_scratch_bytes(int B, int h, int w);
 // deform_kernels.hip: the detection head's deformable attention sampler (epropnp_deform_sample_forward / _backward): one launch each,
 // one wave per (object, head); the backward zero-fills the map gradients it is given and scatters into them with float atomics
 int launch_deform_forward(const float* query, const float* key, const float* value, const float* x2d, const float* mask,

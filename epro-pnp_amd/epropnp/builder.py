@@ -9,10 +9,12 @@ from .camera import PerspectiveCamera
 from .cost_fun import AdaptiveHuberPnPCost, HuberPnPCost
 from .epropnp import EProPnP4DoF, EProPnP6DoF
 from .levenberg_marquardt import LMSolver, RSLMSolver
+from .targets import VolumeCenter
 
 PNP = {c.__name__: c for c in (EProPnP4DoF, EProPnP6DoF, LMSolver, RSLMSolver)}
 CAMERA = {'PerspectiveCamera': PerspectiveCamera}
 COSTFUN = {c.__name__: c for c in (HuberPnPCost, AdaptiveHuberPnPCost)}
+CENTER_TARGETS = {'VolumeCenter': VolumeCenter}      # EPro-PnP-Det/epropnp_det/core/bbox_3d/builder.py: build_center_target
 
 
 def _build(cfg, registry, default_args):
@@ -40,3 +42,7 @@ def build_camera(cfg, **default_args):
 
 def build_cost_fun(cfg, **default_args):
     return _build(cfg, COSTFUN, default_args)
+
+
+def build_center_target(cfg, **default_args):
+    return _build(cfg, CENTER_TARGETS, default_args)

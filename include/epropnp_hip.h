@@ -527,6 +527,60 @@ int epropnp_bev_density(const float* pose_samples /* (S,B,4|7) */, const float* 
                         int32_t origin_y, int32_t window, void* scratch, size_t scratch_bytes, float* density /* (G,H,W) */,
                         int32_t* bins /* (S,B) */, void* stream);
 
+/* Centre targets of the detection head's training step: EPro-PnP-Det core/bbox_3d/center_target.py:42-259, VolumeCenter with the box
+ * mesh (called first thing by deform_pnp_head.py:776-780), without a mesh rasteriser and without a render.  For the box mesh the
+ * rasteriser's near / far depth pair of a pixel is the ray-box slab intersection; the whole target is three launches (a per-object
+ * table; per (image, 16 x 16 tile of output cells) partial sums; a reduce over the tiles in tile order in fp64).  No floating-point
+ * atomics: two calls agree to the last bit.  Every output element is written.  No allocation, no synchronisation; capturable into a
+ * hipGraph.  No input value ever forms an address.
+ *
+ * Inputs: bboxes_3d (num_obj,7) = [l, h, w, x, y, z, yaw]; objects sorted by image, image g owns obj_offsets[g] .. obj_offsets[g+1] - 1
+ * (obj_offsets (num_img + 1,), clamped into [0, num_obj]; offsets that do not ascend are not detected; an object in no image is
+ * invalid); cam_intrinsic (num_img,3,3); dense_x2d (num_img,2,h_out,w_out), the original-image pixel coordinates (x, y) of each output
+ * cell; dense_mask (num_img,1,h_out,w_out).
+ * Render grid: h_rend x w_rend pixels (the reference's pad_shape // render_stride, pad_shape = ceil(max_shape / output_stride) *
+ * output_stride).  Render pixel (row r, col c) has its centre at original-image coordinates u = render_stride (c + 0.5) - 0.5,
+ * v = render_stride (r + 0.5) - 0.5 (pixel centres at integers); its ray is d = ((u - cx) / fx, (v - cy) / fy, 1), so the ray
+ * parameter is camera depth.
+ * Box: vertices +-0.5 [l, h, w] rotated about y by yaw ([[c,0,s],[0,1,0],[-s,0,c]]) and translated by [x, y, z]; the slab test in the box
+ * frame gives t_near and t_far.  Each of the two that exists and is > z_clip is a fragment of the ray (the rasteriser clips at z_clip
+ * and leaves the mesh open).
+ * Valid pixel of an object: both fragments exist (t_far > t_near > z_clip) and the number of fragments of the objects of the same
+ * image at that pixel with depth < t_far, the object's own near fragment included, is < faces_per_pixel (0: no limit; where 2 x the
+ * image's objects <= faces_per_pixel the count cannot bind and is skipped).  thickness = t_far - t_near where valid, else 0.
+ * Output cell (i, j) of the object's image: the bilinear sample (zeros outside, align_corners False) of thickness and of the 0 / 1
+ * valid map at render coordinates ((x + 0.5) / render_stride - 0.5, (y + 0.5) / render_stride - 0.5), both times the mask value; the four
+ * taps are four ray-box tests.  A cell with a coordinate that is not finite contributes nothing.
+ * centers_2d (num_obj,2): with p = (j output_stride + output_stride / 2, i output_stride + output_stride / 2) and W = sum t:
+ * sum t p / W; (0, 0) where W = 0.
+ * bboxes_2d (num_obj,4): get_bbox_2d != 0: over the cells whose resampled valid value is >= 0.5, x1 = min j output_stride, x2 = max j
+ * output_stride + output_stride, y alike; [w_out output_stride, h_out output_stride, output_stride, output_stride] without such a
+ * cell.  get_bbox_2d == 0: a copy of bboxes_2d_in (num_obj,4), which may be NULL otherwise.
+ * valid (num_obj,) bytes: W >= 1e-6 and both box sides >= min_box_size.  A box or intrinsics that are not finite (or a zero focal
+ * length): valid = 0, centre (0, 0).
+ *
+ * epropnp_box_thickness: what the fused pass never stores -- thickness (num_obj,h_rend,w_rend) and valid (num_obj,h_rend,w_rend)
+ * bytes per render pixel, through the same device function.
+ *
+ * scratch: at least epropnp_volume_centers_scratch_bytes(num_obj, h_out, w_out) bytes, 8-byte aligned: 64 bytes per object plus 40
+ * bytes per (tile, object); epropnp_box_thickness takes the size with h_out = w_out = 0.
+ * num_obj == 0 launches nothing and follows no pointer.
+ * EPROPNP_EINVAL: a negative count, num_img > 65535 (epropnp_box_thickness: num_obj > 65535), objects without an image, a size
+ * outside 1 .. 4096, a stride < 1, faces_per_pixel < 2 other than 0, a negative z_clip, a NULL pointer with num_obj > 0, scratch_bytes
+ * below the size query. */
+size_t epropnp_volume_centers_scratch_bytes(int32_t num_obj, int32_t h_out, int32_t w_out);
+int epropnp_volume_centers(const float* bboxes_3d /* (B,7) */, const float* bboxes_2d_in /* (B,4) or NULL */,
+                           const int32_t* obj_offsets /* (G+1,) */, const float* cam_intrinsic /* (G,3,3) */,
+                           const float* dense_x2d /* (G,2,h,w) */, const float* dense_mask /* (G,1,h,w) */, int32_t num_obj,
+                           int32_t num_img, int32_t h_out, int32_t w_out, int32_t h_rend, int32_t w_rend, int32_t output_stride,
+                           int32_t render_stride, int32_t faces_per_pixel, float z_clip, float min_box_size, int32_t get_bbox_2d,
+                           void* scratch, size_t scratch_bytes, float* centers_2d /* (B,2) */, float* bboxes_2d /* (B,4) */,
+                           uint8_t* valid /* (B,) */, void* stream);
+int epropnp_box_thickness(const float* bboxes_3d /* (B,7) */, const int32_t* obj_offsets /* (G+1,) */,
+                          const float* cam_intrinsic /* (G,3,3) */, int32_t num_obj, int32_t num_img, int32_t h_rend, int32_t w_rend,
+                          int32_t render_stride, int32_t faces_per_pixel, float z_clip, void* scratch, size_t scratch_bytes,
+                          float* thickness /* (B,Hr,Wr) */, uint8_t* valid /* (B,Hr,Wr) */, void* stream);
+
 int epropnp_abi_version(void);
 const char* epropnp_last_error(void);
 
@@ -534,7 +588,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "box_overlap", "box_overlap_segmented", "orient_density", "bev_density", "kitti_match", "kitti_thresholds", "kitti_statistics") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "box_overlap", "box_overlap_segmented", "orient_density", "bev_density", "kitti_match", "kitti_thresholds", "kitti_statistics", "volume_centers", "box_thickness") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
