@@ -237,36 +237,72 @@ __global__ __launch_bounds__(256) void cost_pose_cam_grad_kernel(Problem p, cons
 
 // ----------------------------------------------------------------------------------------------------------
 // Glue of the training step that the reference leaves to ~25 small ATen launches: adaptive Huber threshold and the
-// Monte-Carlo pose loss.  Both are single HBM-bound passes.
+// Monte-Carlo pose loss.  Both read their inputs from HBM once.
+constexpr int kDeltaResident = 4;      // points a thread keeps in registers (launch_adaptive_delta: threads * 4 >= N up to N = 1024)
 __global__ __launch_bounds__(256) void adaptive_delta_kernel(const float* __restrict__ x2d, const float* __restrict__ w2d,
                                                               int B, int N, float rel, float* __restrict__ delta,
                                                               float* __restrict__ stats) {
-  __shared__ float red[5 * 16];
+  __shared__ float red[4 * 16];
   const int b = object_of_block(B);
   if (b >= B) return;
   const float2* x = reinterpret_cast<const float2*>(x2d) + (size_t)b * N;
   const float2* w = reinterpret_cast<const float2*>(w2d) + (size_t)b * N;
-  // shifted one-pass moments (pivot = first point) -> no E[x^2] - E[x]^2 cancellation at pixel magnitudes
-  const float2 piv = x[0];
-  float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int n = (int)threadIdx.x; n < N; n += (int)blockDim.x) {
-    const float2 xi = x[n], wi = w[n];
-    const float dx = xi.x - piv.x, dy = xi.y - piv.y;
-    v[0] += wi.x + wi.y;
-    v[1] += dx; v[2] += dy;
-    v[3] += dx * dx; v[4] += dy * dy;
+  const float n = (float)N;
+  const int T = (int)blockDim.x, tid = (int)threadIdx.x;
+  // Two passes over the object's points.  Pass 1: the mean, summed as offsets from the first point (identical points give that point
+  // exactly, hence sd == 0 exactly).  Pass 2: moments of the deviations from that mean.  A one-pass sum of squares about the first
+  // point cancels in  sum d^2 - (sum d)^2 / n  by (distance of that point / sd)^2: an outlier at index 0 cost three digits of delta
+  // at N = 4096.  Up to N = 1024 the launcher gives a thread at most four points: they stay in registers, all loads in flight at
+  // once, and pass 2 reads no memory; beyond, pass 2 finds the object's 8 N bytes in L1 / L2.  Either way a thread takes its points
+  // in ascending order: the same sums.
+  const bool resident = N <= kDeltaResident * T;
+  float2 xr[kDeltaResident], wr[kDeltaResident];
+  if (resident) {
+#pragma unroll
+    for (int k = 0; k < kDeltaResident; ++k) {
+      const int i = min(tid + k * T, N - 1);      // (the loads are unconditional, the sums below masked)
+      xr[k] = x[i]; wr[k] = w[i];
+    }
   }
-  block_sum<5>(v, red);
+  const float2 piv = x[0];
+  float s[3] = {0.f, 0.f, 0.f};
+  auto first = [&](const float2 xi, const float2 wi) {
+    s[0] += wi.x + wi.y;
+    s[1] += xi.x - piv.x; s[2] += xi.y - piv.y;
+  };
+  if (resident) {
+#pragma unroll
+    for (int k = 0; k < kDeltaResident; ++k)
+      if (tid + k * T < N) first(xr[k], wr[k]);
+  } else {
+    for (int i = tid; i < N; i += T) first(x[i], w[i]);
+  }
+  block_sum<3>(s, red);
+  const float mx = piv.x + s[1] / n, my = piv.y + s[2] / n;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  auto second = [&](const float2 xi) {
+    const float dx = xi.x - mx, dy = xi.y - my;
+    v[0] += dx; v[1] += dy;
+    v[2] += dx * dx; v[3] += dy * dy;
+  };
+  if (resident) {
+#pragma unroll
+    for (int k = 0; k < kDeltaResident; ++k)
+      if (tid + k * T < N) second(xr[k]);
+  } else {
+    for (int i = tid; i < N; i += T) second(x[i]);
+  }
+  block_sum<4>(v, red);
   if (threadIdx.x == 0) {
-    const float n = (float)N;
-    const float var = ((v[3] - v[1] * v[1] / n) + (v[4] - v[2] * v[2] / n)) / (n - 1.0f);
-    const float sd = sqrtf(fmaxf(var, 0.f));
-    const float mw = v[0] / (2.0f * n);
+    // (sum d)^2 / n takes out what the rounding of the mean left in sum d^2 (second order: no cancellation)
+    const float var = ((v[2] - v[0] * v[0] / n) + (v[3] - v[1] * v[1] / n)) / (n - 1.0f);
+    const float sd = sqrtf(var < 0.f ? 0.f : var);      // only a negative rounding residue is clamped: NaN (non-finite input, N = 1) stays
+    const float mw = s[0] / (2.0f * n);
     delta[b] = mw * sd * rel;
     stats[(size_t)b * 4 + 0] = mw;
     stats[(size_t)b * 4 + 1] = sd;
-    stats[(size_t)b * 4 + 2] = piv.x + v[1] / n;
-    stats[(size_t)b * 4 + 3] = piv.y + v[2] / n;
+    stats[(size_t)b * 4 + 2] = mx + v[0] / n;
+    stats[(size_t)b * 4 + 3] = my + v[1] / n;
   }
 }
 
@@ -789,7 +825,7 @@ int launch_shift_poses_pair(const float* pose_a, float* out_a, int Pa, const flo
 //   x3d = noc * dim                                   (EPro-PnP-6DoF/lib/train.py:141, Det deform_pnp_head.py:873)
 //   mode 0: w2d = softmax_N(logits) * scale           (Det deform_pnp_head.py:418-423,874)
 //   mode 1: w2d = exp(logits - mean_N(logits) - log N) * scale     ("mean-normalised exp", lib/train.py:163-166)
-// One workgroup per object; stats[b] = {max or mean (x, y), sum of exponentials (x, y)} is kept for the backward.
+// One workgroup per object; stats[b] = {max or mean (x, y), sum of exponentials (x, y) (mode 0; mode 1: N, unread)} is kept for the backward.
 //
 // Two input layouts.  Point-major: noc (B,N,3), logits (B,N,2).  Dense (lib/train.py:143-162): the network's maps
 // noc (B,3,H*W), logits (B,2,H*W) gathered at inds (B,N) -- `x.flatten(2).transpose(-1,-2)[batch_inds, sample_inds]`
@@ -841,7 +877,7 @@ __global__ __launch_bounds__(256) void prepare_forward_kernel(const float* __res
                                                                const float* __restrict__ logits,
                                                                const float* __restrict__ scale, PrepLayout L,
                                                                const float* __restrict__ box, int B, int N, int mode,
-                                                               float* __restrict__ x3d, float* __restrict__ x2d,
+                                                               float log_n, float* __restrict__ x3d, float* __restrict__ x2d,
                                                                float* __restrict__ w2d, float* __restrict__ stats) {
   __shared__ float scratch[4 * 4];
   const int b = object_of_block(B);
@@ -873,14 +909,16 @@ __global__ __launch_bounds__(256) void prepare_forward_kernel(const float* __res
     }
     block_sum<2>(se, scratch);
   } else {
-    se[0] = se[1] = (float)N;                // exp(l - mean - log N) = exp(l - mean) / N
+    se[0] = se[1] = (float)N;                // stats[2:4], informational (include/epropnp_hip.h): mode 1 normalises inside the exponent, log_n
   }
   const float sx = scale ? scale[(size_t)b * 2] : 1.f, sy = scale ? scale[(size_t)b * 2 + 1] : 1.f;
-  const float kx = sx / se[0], ky = sy / se[1];
+  // mode 1: exp(l - mean - log N) as the reference writes it -- exp(l - mean) / N is inf for l - mean in (88.7, 88.7 + log N),
+  // where the weight itself is finite.  (mode 0: log_n = 0, l - max <= 0.)
+  const float kx = (mode == 0) ? sx / se[0] : sx, ky = (mode == 0) ? sy / se[1] : sy;
   float2* wo = reinterpret_cast<float2*>(w2d) + (size_t)b * N;
   for (int n = tid; n < N; n += T) {
     const float2 v = prep_ld2(logits, b, n, N, L);
-    wo[n] = make_float2(expf(v.x - ref[0]) * kx, expf(v.y - ref[1]) * ky);
+    wo[n] = make_float2(expf((v.x - ref[0]) - log_n) * kx, expf((v.y - ref[1]) - log_n) * ky);
   }
   if (x3d != nullptr) {
     const float d0 = dim[(size_t)b * 3], d1 = dim[(size_t)b * 3 + 1], d2 = dim[(size_t)b * 3 + 2];
@@ -914,7 +952,7 @@ __global__ __launch_bounds__(256) void prepare_backward_kernel(const float* __re
                                                                 const float* __restrict__ stats,
                                                                 const float* __restrict__ gx3d,
                                                                 const float* __restrict__ gw2d, int B, int N, int mode,
-                                                                float* __restrict__ gnoc, float* __restrict__ gdim,
+                                                                float log_n, float* __restrict__ gnoc, float* __restrict__ gdim,
                                                                 float* __restrict__ glogits, float* __restrict__ gscale) {
   __shared__ float scratch[5 * 4];
   const int b = object_of_block(B);
@@ -922,14 +960,15 @@ __global__ __launch_bounds__(256) void prepare_backward_kernel(const float* __re
   const int T = (int)blockDim.x, tid = (int)threadIdx.x;
   const float2* gw = reinterpret_cast<const float2*>(gw2d) + (size_t)b * N;
   const float r0 = stats[(size_t)b * 4], r1 = stats[(size_t)b * 4 + 1];
-  const float ie0 = 1.0f / stats[(size_t)b * 4 + 2], ie1 = 1.0f / stats[(size_t)b * 4 + 3];
+  // p as the forward computed it: mode 0 exp(l - max) / sum, mode 1 exp(l - mean - log N)
+  const float ie0 = (mode == 0) ? 1.0f / stats[(size_t)b * 4 + 2] : 1.0f, ie1 = (mode == 0) ? 1.0f / stats[(size_t)b * 4 + 3] : 1.0f;
   const float sx = scale ? scale[(size_t)b * 2] : 1.f, sy = scale ? scale[(size_t)b * 2 + 1] : 1.f;
   // sums: sum_n g_n p_n per channel (p = normalised exponential without the scale), sum_n gx3d_n * noc_n per axis
   float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   for (int n = tid; n < N; n += T) {
     const float2 v = prep_ld2(logits, b, n, N, L), g = gw[n];
-    s[0] = fmaf(g.x, expf(v.x - r0) * ie0, s[0]);
-    s[1] = fmaf(g.y, expf(v.y - r1) * ie1, s[1]);
+    s[0] = fmaf(g.x, expf((v.x - r0) - log_n) * ie0, s[0]);
+    s[1] = fmaf(g.y, expf((v.y - r1) - log_n) * ie1, s[1]);
     if (gx3d != nullptr) {
       const size_t o = ((size_t)b * N + n) * 3;
       float c[3];
@@ -943,7 +982,7 @@ __global__ __launch_bounds__(256) void prepare_backward_kernel(const float* __re
   const float invn = 1.0f / (float)N;
   for (int n = tid; n < N; n += T) {
     const float2 v = prep_ld2(logits, b, n, N, L), g = gw[n];
-    const float px = expf(v.x - r0) * ie0, py = expf(v.y - r1) * ie1;
+    const float px = expf((v.x - r0) - log_n) * ie0, py = expf((v.y - r1) - log_n) * ie1;
     float ox, oy;
     if (mode == 0) {
       ox = sx * px * (g.x - s[0]); oy = sy * py * (g.y - s[1]);
@@ -965,6 +1004,9 @@ __global__ __launch_bounds__(256) void prepare_backward_kernel(const float* __re
   }
 }
 
+// log N of the mean-normalised exponential, rounded once from double as the reference's `- math.log(N)`; 0 for softmax
+static float prepare_log_n(int N, int mode) { return mode == 1 ? (float)log((double)N) : 0.f; }
+
 static int prepare_threads(int N) {
   int t = 64;
   while (t < 256 && t * 2 < N) t *= 2;
@@ -978,7 +1020,7 @@ int launch_prepare_forward(const float* noc, const float* dim, const float* logi
     return fail(EPROPNP_EINVAL, "prepare_forward: bad argument");
   const PrepLayout L = {nullptr, 0, 0};
   PNP_LAUNCH(prepare_forward_kernel, dim3(padded_object_grid(B)), dim3(prepare_threads(N)), 0, st, noc, dim, logits, scale, L,
-             (const float*)nullptr, B, N, mode, x3d, (float*)nullptr, w2d, stats);
+             (const float*)nullptr, B, N, mode, prepare_log_n(N, mode), x3d, (float*)nullptr, w2d, stats);
   return check_launch("prepare_forward_kernel");
 }
 
@@ -991,7 +1033,7 @@ int launch_prepare_backward(const float* noc, const float* dim, const float* log
     return fail(EPROPNP_EINVAL, "prepare_backward: bad argument");
   const PrepLayout L = {nullptr, 0, 0};
   PNP_LAUNCH(prepare_backward_kernel, dim3(padded_object_grid(B)), dim3(prepare_threads(N)), 0, st, noc, dim, logits, scale, L,
-             stats, gx3d, gw2d, B, N, mode, gnoc, gdim, glogits, gscale);
+             stats, gx3d, gw2d, B, N, mode, prepare_log_n(N, mode), gnoc, gdim, glogits, gscale);
   return check_launch("prepare_backward_kernel");
 }
 
@@ -1004,7 +1046,7 @@ int launch_prepare_dense_forward(const float* noc_map, const float* dim, const f
     return fail(EPROPNP_EINVAL, "prepare_dense_forward: bad argument");
   const PrepLayout L = {inds, H * W, W};
   PNP_LAUNCH(prepare_forward_kernel, dim3(padded_object_grid(B)), dim3(prepare_threads(N)), 0, st, noc_map, dim, logit_map,
-             scale, L, box, B, N, mode, x3d, x2d, w2d, stats);
+             scale, L, box, B, N, mode, prepare_log_n(N, mode), x3d, x2d, w2d, stats);
   return check_launch("prepare_forward_kernel (dense)");
 }
 
@@ -1022,7 +1064,7 @@ int launch_prepare_dense_backward(const float* noc_map, const float* dim, const 
   if (gx3d != nullptr && launch_fill_u32(gnoc_map, 0u, (size_t)B * 3 * plane / 4, st) != EPROPNP_OK)
     return fail(EPROPNP_ELAUNCH, "prepare_dense_backward: memset");
   PNP_LAUNCH(prepare_backward_kernel, dim3(padded_object_grid(B)), dim3(prepare_threads(N)), 0, st, noc_map, dim, logit_map,
-             scale, L, stats, gx3d, gw2d, B, N, mode, gnoc_map, gdim, glogit_map, gscale);
+             scale, L, stats, gx3d, gw2d, B, N, mode, prepare_log_n(N, mode), gnoc_map, gdim, glogit_map, gscale);
   return check_launch("prepare_backward_kernel (dense)");
 }
 

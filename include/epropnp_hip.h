@@ -730,7 +730,9 @@ int epropnp_amis_backward_split_costs(const epropnp_problem* prob, const float* 
 /* AdaptiveHuberPnPCost.set_param (epropnp/cost_fun.py:123-126):
  *   delta[b] = mean(w2d[b]) * sqrt(sum_xy var_N(x2d[b])) * relative_delta      (unbiased variance)
  * x2d (B,N,2), w2d (B,N,2) -> delta (B,), stats (B,4) = [mean_w, x2d_std, mean_x, mean_y] (kept for the backward,
- * which is three broadcast expressions evaluated by the caller). */
+ * which is three broadcast expressions evaluated by the caller).  The variance is taken about the mean (two passes inside the
+ * launch): its accuracy does not depend on where any one point lies.  As in the reference, a NaN or an infinity in x2d, a NaN in w2d
+ * and num_pts = 1 (0 / 0) give delta = NaN; identical points give exactly 0. */
 int epropnp_adaptive_delta(const float* x2d, const float* w2d, int32_t num_obj, int32_t num_pts, float relative_delta,
                            float* delta, float* stats, void* stream);
 
@@ -815,7 +817,9 @@ int epropnp_shift_poses(const float* pose, const float* offset, int32_t num_pose
  *   mode 0: w2d = softmax_N(logits) * scale                    Det deform_pnp_head.py:418-423,874
  *   mode 1: w2d = exp(logits - mean_N(logits) - log N) * scale EPro-PnP-6DoF/lib/train.py:163-166
  * noc (B,N,3), dim (B,3) (both NULL with x3d NULL: weights only), logits (B,N,2), scale (B,2) or NULL
- * -> x3d (B,N,3), w2d (B,N,2), stats (B,4) kept for the backward. */
+ * -> x3d (B,N,3), w2d (B,N,2), stats (B,4) kept for the backward: [0:2] the maximum (softmax) or the mean (mean_exp) of the logits
+ * per channel; [2:4] the sum of exponentials (softmax).  For mean_exp [2:4] holds N and is no normaliser: log N sits inside the
+ * exponent, and the backward does not read it. */
 #define EPROPNP_W2D_SOFTMAX 0
 #define EPROPNP_W2D_MEAN_EXP 1
 int epropnp_prepare_forward(const float* noc, const float* dim, const float* logits, const float* scale,
