@@ -14,7 +14,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['eval_kernels.hip', 'lm_kernel.hip', 'amis_kernels.hip', 'amis_forward_mfma.hip', 'amis_backward_mfma.hip', 'gn_step_kernel.hip', 'rslm_kernel.hip', 'mc_forward.hip', 'posterior_kernels.hip', 'metrics_kernels.hip', 'boxes_kernels.hip', 'kitti_eval_kernels.hip', 'density_kernels.hip', 'center_target_kernels.hip', 'deform_kernels.hip', 'roi_kernels.hip', 'roi_align_kernels.hip', 'c_api.hip']
+SOURCES = ['eval_kernels.hip', 'lm_kernel.hip', 'amis_kernels.hip', 'amis_forward_mfma.hip', 'amis_backward_mfma.hip', 'gn_step_kernel.hip', 'rslm_kernel.hip', 'mc_forward.hip', 'posterior_kernels.hip', 'metrics_kernels.hip', 'boxes_kernels.hip', 'kitti_eval_kernels.hip', 'density_kernels.hip', 'center_target_kernels.hip', 'point_target_kernels.hip', 'deform_kernels.hip', 'roi_kernels.hip', 'roi_align_kernels.hip', 'c_api.hip']
 # Every translation unit is compiled WITHOUT the SLP vectoriser (HIP build only).  Two reasons, the second one decisive:
 #  * where the vectoriser packs independent scalar FMAs into v_pk_* it pays for it in v_mov shuffles and gains nothing (packed fp32
 #    issues at half the rate of the scalar form, profiles/r01_ubench_valu_rates.txt): lm 79 -> 70 us at C2, rslm 117 -> 107 us at C4,

@@ -361,6 +361,31 @@ int epropnp_box_thickness(const float* bboxes_3d, const int32_t* obj_offsets, co
                                    faces_per_pixel, z_clip, scratch, scratch_bytes, thickness, valid, (hipStream_t)stream);
 }
 
+// fcos_emb_head.py:299-438 (FCOSEmbHead.get_targets) in one pass over (image, point), outputs in the flattened level-major order
+int epropnp_point_targets(const float* points, const int32_t* lvl_offsets, const float* radius_px, const float* regress_lo,
+                          const float* regress_hi, const int64_t* level_strides, int32_t num_levels, const float* gt_bboxes,
+                          const float* centers2d, const int64_t* gt_labels, const int32_t* img_offsets, int32_t num_points,
+                          int32_t num_gt, int32_t num_img, int32_t num_classes, float centerness_alpha, int64_t* labels,
+                          float* centerness_targets, int64_t* gt_inds, int64_t* strides, int32_t* num_fg, void* stream) {
+  pnp::StageScope prof_("point_targets", (hipStream_t)stream);
+  return pnp::launch_point_targets(points, lvl_offsets, radius_px, regress_lo, regress_hi, (const long long*)level_strides, num_levels,
+                                   gt_bboxes, centers2d, (const long long*)gt_labels, img_offsets, num_points, num_gt, num_img,
+                                   num_classes, centerness_alpha, (long long*)labels, centerness_targets, (long long*)gt_inds,
+                                   (long long*)strides, num_fg, (hipStream_t)stream);
+}
+
+// deform_pnp_head.py:1148-1174 (obj_sampler behind its draws)
+int epropnp_obj_sample_weights(const uint8_t* fg_mask, const float* centerness_targets, const int64_t* gt_inds,
+                               int64_t num_total_point, const int64_t* sample_point_inds, int32_t num_obj_samples,
+                               int32_t num_uniform, float eps, int64_t* sample_gt_inds, float* sample_weights,
+                               float* sample_uniform_weights, int32_t* num_fg, void* stream) {
+  pnp::StageScope prof_("obj_sample_weights", (hipStream_t)stream);
+  return pnp::launch_obj_sample_weights(fg_mask, centerness_targets, (const long long*)gt_inds, (long long)num_total_point,
+                                        (const long long*)sample_point_inds, num_obj_samples, num_uniform, eps,
+                                        (long long*)sample_gt_inds, sample_weights, sample_uniform_weights, num_fg,
+                                        (hipStream_t)stream);
+}
+
 int epropnp_deform_sample_forward(const float* query, const float* key, const float* value, const float* dense_x2d,
                                   const float* dense_mask, const float* sampling_location, const int64_t* obj_img_ind,
                                   int32_t num_obj, int32_t num_img, int32_t num_heads, int32_t num_points, int32_t head_dim,

@@ -336,6 +336,17 @@ int launch_volume_centers(const float* boxes3d, const float* boxes2d_in, const i
 int launch_box_thickness(const float* boxes3d, const int32_t* offsets, const float* cam, int B, int G, int Hr, int Wr, int rs, int K,
                          float zc, void* scratch, size_t scratch_bytes, float* thick, uint8_t* valid, hipStream_t st);
 size_t volume_centers_scratch_bytes(int B, int h, int w);
+// point_target_kernels.hip: the training step's point targets (epropnp_point_targets: a one-word fill and one launch, a workgroup per
+// (tile of points, image) with the image's objects in LDS) and the sampler's weights behind its draws (epropnp_obj_sample_weights:
+// one launch of one workgroup, every sum in a fixed order).  lvl_off .. level_strides are HOST arrays
+int launch_point_targets(const float* points, const int32_t* lvl_off, const float* radius_px, const float* regress_lo,
+                         const float* regress_hi, const long long* level_strides, int L, const float* gt_bboxes, const float* centers2d,
+                         const long long* gt_labels, const int32_t* img_off, int P, int G, int num_img, int num_classes, float alpha,
+                         long long* labels, float* centerness, long long* gt_inds, long long* strides, int32_t* num_fg,
+                         hipStream_t st);
+int launch_obj_sample_weights(const uint8_t* fg_mask, const float* centerness, const long long* gt_inds, long long T,
+                              const long long* sample_point_inds, int N, int num_uniform, float eps, long long* sample_gt_inds,
+                              float* sample_weights, float* sample_uniform_weights, int32_t* num_fg, hipStream_t st);
 // deform_kernels.hip: the detection head's deformable attention sampler (epropnp_deform_sample_forward / _backward): one launch each,
 // one wave per (object, head); the backward zero-fills the map gradients it is given and scatters into them with float atomics
 int launch_deform_forward(const float* query, const float* key, const float* value, const float* x2d, const float* mask,

@@ -32,6 +32,12 @@
 #ifndef PNP_BWD_MINW       // waves per SIMD of the MFMA backward with <= 2 resident point tiles
 #define PNP_BWD_MINW 3
 #endif
+#ifndef PNP_PT_THREADS     // points per workgroup of the point-target kernel, one per lane (point_target_kernels.hip)
+#define PNP_PT_THREADS 256
+#endif
+#ifndef PNP_PT_CHUNK       // objects of an image that kernel stages in LDS at a time (6 floats each); an image with more takes another round
+#define PNP_PT_CHUNK 64
+#endif
 
 // ---- instrumentation ----------------------------------------------------------------------------------------------------------
 #ifdef PNP_TUNING

@@ -124,6 +124,8 @@ def _declare(lib):
     lib.epropnp_volume_centers_scratch_bytes.argtypes = [i32, i32, i32]
     lib.epropnp_volume_centers_scratch_bytes.restype = sz
     i64 = C.c_int64
+    lib.epropnp_point_targets.argtypes = [vp] * 6 + [i32] + [vp] * 4 + [i32] * 4 + [f32] + [vp] * 6
+    lib.epropnp_obj_sample_weights.argtypes = [vp] * 3 + [i64, vp, i32, i32, f32] + [vp] * 5
     lib.epropnp_deform_sample_forward.argtypes = [vp] * 7 + [i32] * 8 + [i64] * 4 + [vp] * 7
     lib.epropnp_deform_sample_backward.argtypes = [vp] * 13 + [i32] * 8 + [i64] * 4 + [vp] * 5
     lib.epropnp_roi_logsumexp_forward.argtypes = [vp] * 2 + [i32] * 4 + [vp] * 2
@@ -179,7 +181,8 @@ def _declare(lib):
                  'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms', 'orient_density',
                  'bev_density', 'deform_sample_forward', 'deform_sample_backward', 'roi_logsumexp_forward',
                  'roi_logsumexp_backward', 'roi_align_forward', 'roi_align_backward', 'box_overlap', 'box_overlap_plan',
-                 'box_overlap_segmented', 'kitti_match', 'kitti_thresholds', 'kitti_statistics', 'volume_centers', 'box_thickness'):
+                 'box_overlap_segmented', 'kitti_match', 'kitti_thresholds', 'kitti_statistics', 'volume_centers', 'box_thickness',
+                 'point_targets', 'obj_sample_weights'):
         getattr(lib, 'epropnp_' + name).restype = C.c_int
     return lib
 
@@ -207,7 +210,7 @@ EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 
            'epropnp_roi_align_backward', 'epropnp_box_overlap', 'epropnp_box_overlap_plan', 'epropnp_box_overlap_segmented',
            'epropnp_kitti_match', 'epropnp_kitti_match_scratch_bytes', 'epropnp_kitti_thresholds', 'epropnp_kitti_statistics',
            'epropnp_kitti_statistics_scratch_bytes', 'epropnp_volume_centers', 'epropnp_volume_centers_scratch_bytes',
-           'epropnp_box_thickness')
+           'epropnp_box_thickness', 'epropnp_point_targets', 'epropnp_obj_sample_weights')
 
 
 def lib():

@@ -581,6 +581,68 @@ int epropnp_box_thickness(const float* bboxes_3d /* (B,7) */, const int32_t* obj
                           int32_t render_stride, int32_t faces_per_pixel, float z_clip, void* scratch, size_t scratch_bytes,
                           float* thickness /* (B,Hr,Wr) */, uint8_t* valid /* (B,Hr,Wr) */, void* stream);
 
+/* Point targets of the detection head's training step: EPro-PnP-Det models/dense_heads/fcos_emb_head.py:299-438,
+ * FCOSEmbHead.get_targets (called by deform_pnp_head.py:808 on the centre targets' output), in one pass over (image, point): a
+ * one-word fill and one launch, a workgroup per (tile of 256 points, image) with the image's objects in LDS, 64 at a time.  No
+ * scratch, no floating-point atomics (num_fg is built with integer adds), no synchronisation: two calls agree to the last bit; capturable
+ * into a hipGraph.  Every output element is written.
+ *
+ * Inputs: points (num_points,2) = (x, y), shared by all images, level 0 first; gt_bboxes (num_gt,4) = [x1, y1, x2, y2]; centers2d
+ * (num_gt,2); gt_labels (num_gt,) int64; objects sorted by image, image i owns img_offsets[i] .. img_offsets[i+1] - 1 (img_offsets
+ * (num_img + 1,) on the device, clamped into [0, num_gt]; offsets that do not ascend are not detected).
+ * HOST arrays, read during the call: lvl_offsets (num_levels + 1,), the starts of the levels in `points` (0 .. num_points, ascending,
+ * num_levels <= 8); per level radius_px = stride x center_sample_radius (> 0), the regress range [regress_lo, regress_hi], and
+ * level_strides (int64; NULL unless `strides` is wanted).
+ * Definition: point (x, y) of level l in image i; each object j of image i in ascending order, with s = radius_px[l]:
+ *   inside:   min(x - (cx - s), y - (cy - s), (cx + s) - x, (cy + s) - y) > 0
+ *   in range: regress_lo[l] <= max(x - x1, y - y1, x2 - x, y2 - y) <= regress_hi[l]
+ *   d_j = sqrtf(dx dx + dy dy), (dx, dy) = (x - cx, y - cy), each product and the sum rounded on its own (no fused multiply-add, so
+ *   that objects mirrored about a point give equal bits), when both hold, else 1e8.
+ * The winner is the lowest j with the smallest d_j (strict < while scanning: torch.min's first-minimum rule).  A comparison with a NaN
+ * operand is false: an object with a NaN among its six numbers never wins.
+ *   labels = gt_labels[winner], or num_classes when the smallest d is 1e8;
+ *   centerness_targets = expf(-centerness_alpha (d_min / (1.414f s))), which underflows to 0 for background;
+ *   gt_inds = img_offsets[i] + winner; the winner of an all-background row is local index 0, and so is that of an image without
+ *   objects (label num_classes, centerness 0): what the reference returns for both;
+ *   strides (optional, NULL: not wanted) = level_strides[l] (deform_pnp_head.py:825-827).
+ * Outputs, all (num_img num_points,) in the reference's flattened order -- level-major, then image, then the point within the level,
+ * i.e. torch.cat of get_targets' per-level lists: element num_img lvl_offsets[l] + i n_l + (p - lvl_offsets[l]), n_l the level's
+ * points.  num_fg (1,) int32: the number of elements with label < num_classes.
+ * num_points == 0 or num_img == 0: nothing is launched, no pointer is followed and num_fg is not written.
+ * EPROPNP_EINVAL: a negative count, num_levels outside 1 .. 8, num_img > 65535, a NaN centerness_alpha, lvl_offsets that do not run
+ * from 0 to num_points ascending, a radius_px that is not > 0, a NaN regress range, strides without level_strides, a NULL pointer
+ * that would be followed. */
+int epropnp_point_targets(const float* points /* (P,2) */, const int32_t* lvl_offsets /* host (L+1,) */,
+                          const float* radius_px /* host (L,) */, const float* regress_lo /* host (L,) */,
+                          const float* regress_hi /* host (L,) */, const int64_t* level_strides /* host (L,) or NULL */,
+                          int32_t num_levels, const float* gt_bboxes /* (G,4) */, const float* centers2d /* (G,2) */,
+                          const int64_t* gt_labels /* (G,) */, const int32_t* img_offsets /* (num_img+1,) */, int32_t num_points,
+                          int32_t num_gt, int32_t num_img, int32_t num_classes, float centerness_alpha,
+                          int64_t* labels /* (num_img P,) */, float* centerness_targets /* (num_img P,) */,
+                          int64_t* gt_inds /* (num_img P,) */, int64_t* strides /* (num_img P,) or NULL */, int32_t* num_fg /* (1,) */,
+                          void* stream);
+
+/* The object sampler of the same step behind its draws: deform_pnp_head.py:1148-1174 (obj_sampler), one launch of one workgroup.
+ * With fg = fg_mask != 0 (bytes), c = centerness_targets, S = sum of c over the foreground, n = its count,
+ * u = min(num_uniform, n) / num_obj_samples:
+ *   prob_k = c_k fg_k / max(S, eps);  prob_mix_k = fg_k / max(n, 1) u + prob_k (1 - u);
+ * per sample i with its drawn point p_i = sample_point_inds[i] (clamped into the points before it forms an address):
+ *   sample_gt_inds_i = gt_inds[p_i];  w_i = prob / prob_mix at p_i;
+ *   sample_weights_i = w_i / max(sum of w_j over the samples j with the same gt index, eps), divided by max(their mean, eps);
+ *   sample_uniform_weights_i = 1 / max(number of samples with the same gt index, 1), divided by max(their mean, eps).
+ * max(v, least) keeps a NaN v, as torch's clamp(min=) does (a drawn point outside the foreground gives 0 / 0).  Every sum runs in a
+ * fixed order in fp64 -- thread t of 1024 over the points t, t + 1024, ..., then a binary tree; per sample over the samples in
+ * ascending order -- so two calls agree to the last bit; samples are grouped by comparing their gt indices: no (num_gt, N) mask and
+ * no largest index.  num_fg (1,) int32, optional (NULL: not wanted): n.  No scratch, no allocation, no synchronisation.
+ * num_obj_samples == 0 launches nothing and follows no pointer.
+ * EPROPNP_EINVAL: a negative count, num_obj_samples > 2048, num_uniform outside 0 .. num_obj_samples, eps that is not > 0, samples
+ * without points, a NULL pointer that would be followed. */
+int epropnp_obj_sample_weights(const uint8_t* fg_mask /* (T,) */, const float* centerness_targets /* (T,) */,
+                               const int64_t* gt_inds /* (T,) */, int64_t num_total_point,
+                               const int64_t* sample_point_inds /* (N,) */, int32_t num_obj_samples, int32_t num_uniform, float eps,
+                               int64_t* sample_gt_inds /* (N,) */, float* sample_weights /* (N,) */,
+                               float* sample_uniform_weights /* (N,) */, int32_t* num_fg /* (1,) or NULL */, void* stream);
+
 int epropnp_abi_version(void);
 const char* epropnp_last_error(void);
 
@@ -588,7 +650,7 @@ const char* epropnp_last_error(void);
  * epropnp_monte_carlo_forward -- is bracketed by two HIP events on its launch stream.  epropnp_profile_read synchronises
  * on the recorded events of `stage` ("evaluate_cost", "normal_equations", "lm_solve", "rslm_solve", "amis_forward",
  * "amis_backward", "adaptive_delta", "mc_loss_forward", "mc_loss_backward", "gn_step_forward", "gn_step_backward",
- * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "box_overlap", "box_overlap_segmented", "orient_density", "bev_density", "kitti_match", "kitti_thresholds", "kitti_statistics", "volume_centers", "box_thickness") and returns their mean duration and count; bench.py's per-kernel times and roofline
+ * "center_points", "shift_poses", "weight_stats", "posterior_summary", "posterior_resample", "posterior_modes", "pose_errors", "bev_overlap", "bev_nms", "box_overlap", "box_overlap_segmented", "orient_density", "bev_density", "kitti_match", "kitti_thresholds", "kitti_statistics", "volume_centers", "box_thickness", "point_targets", "obj_sample_weights") and returns their mean duration and count; bench.py's per-kernel times and roofline
  * figures come from here.  Not for use inside a hipGraph capture. */
 int epropnp_profile_enable(int on);
 int epropnp_profile_reset(void);
