@@ -169,6 +169,64 @@ struct ProblemTensors {      // contiguous fp32 device tensors behind an epropnp
   }
 };
 
+ProblemTensors problem_tensors(const Tensor& x3d_c, const Tensor& x2d_c, const Tensor& w2d_c, const Tensor& cam_c,
+                               const OptTensor& lb_c, const OptTensor& ub_c, const Tensor& delta_c, const OptTensor& status,
+                               double z_min, double huber_eps, int64_t dof) {
+  ProblemTensors pt;
+  pt.x3d = x3d_c; pt.x2d = x2d_c; pt.w2d = w2d_c; pt.cam = cam_c; pt.delta = delta_c;
+  if (lb_c.has_value() && ub_c.has_value()) { pt.lb = *lb_c; pt.ub = *ub_c; }
+  if (status.has_value()) pt.status = *status;
+  pt.z_min = z_min; pt.huber_eps = huber_eps; pt.dof = dof;
+  return pt;
+}
+
+// What a recompute backward needs of the forward's problem `pt`, into saved_data: its tensors with `x3d` as the points the backward
+// sweeps (the centred ones under normalize), its scalars, the delta fold, and the version counters of the caller-visible inputs
+// (the contiguous views share their version counters when no copy was made; guard_x3d keeps the un-centred points alive for the check).
+// delta_stats: delta = adaptive_delta(., w2d) of THIS w2d -- the backward kernel adds grad_delta's way into grad_w2d itself
+// (epropnp_problem.delta_stats) and delta receives no gradient from the node.
+void save_problem(AutogradContext* ctx, const ProblemTensors& pt, const Tensor& x3d, const OptTensor& delta_stats,
+                  double delta_rel) {
+  auto maybe = [](const Tensor& t) { return t.defined() ? c10::IValue(t) : c10::IValue(); };
+  ctx->saved_data["x3d"] = x3d;
+  ctx->saved_data["x2d"] = pt.x2d; ctx->saved_data["w2d"] = pt.w2d; ctx->saved_data["cam"] = pt.cam;
+  ctx->saved_data["delta"] = pt.delta;
+  ctx->saved_data["lb"] = maybe(pt.lb);
+  ctx->saved_data["ub"] = maybe(pt.ub);
+  ctx->saved_data["z_min"] = pt.z_min; ctx->saved_data["huber_eps"] = pt.huber_eps; ctx->saved_data["dof"] = pt.dof;
+  const bool fold = delta_stats.has_value() && delta_stats->defined();
+  ctx->saved_data["dstats"] = fold ? c10::IValue(delta_stats->detach().contiguous()) : c10::IValue();
+  ctx->saved_data["drel"] = delta_rel;
+  std::vector<int64_t> vers;
+  for (const Tensor* t : {&pt.x3d, &pt.x2d, &pt.w2d, &pt.delta, &pt.cam}) vers.push_back((int64_t)t->_version());
+  ctx->saved_data["guard_x3d"] = pt.x3d;
+  ctx->saved_data["versions"] = vers;
+}
+
+// the problem of save_problem (status: the library's default word; dstats defined = the delta fold is on)
+ProblemTensors load_problem(AutogradContext* ctx) {
+  ProblemTensors pt;
+  pt.x3d = ctx->saved_data["x3d"].toTensor(); pt.x2d = ctx->saved_data["x2d"].toTensor();
+  pt.w2d = ctx->saved_data["w2d"].toTensor(); pt.cam = ctx->saved_data["cam"].toTensor();
+  pt.delta = ctx->saved_data["delta"].toTensor();
+  if (!ctx->saved_data["lb"].isNone()) { pt.lb = ctx->saved_data["lb"].toTensor(); pt.ub = ctx->saved_data["ub"].toTensor(); }
+  pt.z_min = ctx->saved_data["z_min"].toDouble(); pt.huber_eps = ctx->saved_data["huber_eps"].toDouble();
+  pt.dof = ctx->saved_data["dof"].toInt();
+  if (!ctx->saved_data["dstats"].isNone()) { pt.dstats = ctx->saved_data["dstats"].toTensor(); pt.drel = ctx->saved_data["drel"].toDouble(); }
+  return pt;
+}
+
+void check_unmodified(AutogradContext* ctx, const ProblemTensors& pt) {
+  const auto vers = ctx->saved_data["versions"].toIntVector();
+  const Tensor gx3d0 = ctx->saved_data["guard_x3d"].toTensor();
+  const Tensor* ts[5] = {&gx3d0, &pt.x2d, &pt.w2d, &pt.delta, &pt.cam};
+  for (int i = 0; i < 5; ++i)
+    TORCH_CHECK((int64_t)ts[i]->_version() == vers[i],
+                "one of the variables needed for gradient computation has been modified by an inplace operation "
+                "(EPro-PnP recomputes its backward from x3d / x2d / w2d / delta / cam_mats: they must stay unchanged "
+                "between forward and backward)");
+}
+
 // costs (S,B) / cost_init (B,): the forward's sample costs and its cost of pose_init -- the threshold's gradient is taken from them
 // (include/epropnp_hip.h); undefined tensors = the entries without costs
 int backward_launch(const epropnp_problem& q, const Tensor& samples, const Tensor& glw, const Tensor& pin, const Tensor& gin,
@@ -206,11 +264,7 @@ struct FusedMonteCarlo : public torch::autograd::Function<FusedMonteCarlo> {
                 sizeof(epropnp_mc_params));
     epropnp_mc_params par;
     std::memcpy(&par, mc_params.data(), sizeof(par));
-    ProblemTensors pt;
-    pt.x3d = x3d_c; pt.x2d = x2d_c; pt.w2d = w2d_c; pt.cam = cam_c; pt.delta = delta_c;
-    if (lb_c.has_value() && ub_c.has_value()) { pt.lb = *lb_c; pt.ub = *ub_c; }
-    if (status.has_value()) pt.status = *status;
-    pt.z_min = z_min; pt.huber_eps = huber_eps; pt.dof = dof;
+    ProblemTensors pt = problem_tensors(x3d_c, x2d_c, w2d_c, cam_c, lb_c, ub_c, delta_c, status, z_min, huber_eps, dof);
     const epropnp_problem prob = pt.c();
     const int64_t B = prob.num_obj, N = prob.num_pts, PL = dof == 6 ? 7 : 4, d = dof, S = par.amis.mc_samples;
     const auto opt = x2d_c.options();
@@ -240,25 +294,10 @@ struct FusedMonteCarlo : public torch::autograd::Function<FusedMonteCarlo> {
     ctx->save_for_backward({samples_n, costs});
     // (the forward's cost of pose_init, detached: an OUTPUT of this node must not be saved as it is -- it would own the node)
     ctx->saved_data["cost_init"] = cost_init.defined() ? c10::IValue(cost_init.detach()) : c10::IValue();
-    ctx->saved_data["x3d"] = normalize ? x3d_ctr : x3d_c;
-    ctx->saved_data["x2d"] = x2d_c; ctx->saved_data["w2d"] = w2d_c; ctx->saved_data["cam"] = cam_c;
-    ctx->saved_data["delta"] = delta_c;
-    ctx->saved_data["lb"] = pt.lb.defined() ? c10::IValue(pt.lb) : c10::IValue();
-    ctx->saved_data["ub"] = pt.ub.defined() ? c10::IValue(pt.ub) : c10::IValue();
+    save_problem(ctx, pt, normalize ? x3d_ctr : x3d_c, delta_stats, delta_rel);
     ctx->saved_data["pin"] = pin.defined() ? c10::IValue(normalize ? pin_n : pin) : c10::IValue();
-    ctx->saved_data["z_min"] = z_min; ctx->saved_data["huber_eps"] = huber_eps; ctx->saved_data["dof"] = dof;
     ctx->saved_data["nsplit"] = nsplit; ctx->saved_data["stream"] = stream;
     ctx->saved_data["delta_dim"] = (delta.has_value() && delta->defined()) ? (int64_t)delta->dim() : (int64_t)-1;
-    // delta = adaptive_delta(., w2d) of THIS w2d: the backward kernel adds grad_delta's way into grad_w2d itself
-    // (epropnp_problem.delta_stats) and delta receives no gradient from this node
-    const bool fold = delta_stats.has_value() && delta_stats->defined();
-    ctx->saved_data["dstats"] = fold ? c10::IValue(delta_stats->detach().contiguous()) : c10::IValue();
-    ctx->saved_data["drel"] = delta_rel;
-    // version guard on the caller-visible inputs (the contiguous views share their version counters when no copy was made)
-    std::vector<int64_t> vers;
-    for (const Tensor* t : {&x3d_c, &x2d_c, &w2d_c, &delta_c, &cam_c}) vers.push_back((int64_t)t->_version());
-    ctx->saved_data["guard_x3d"] = x3d_c;      // keeps the un-centred points alive for the version check
-    ctx->saved_data["versions"] = vers;
     ctx->set_materialize_grads(false);
     // an autograd node cannot return undefined tensors: absent outputs travel as 0-element placeholders (B > 0 here)
     auto some = [&](const Tensor& t) { return t.defined() ? t : torch::empty({0}, opt); };
@@ -274,25 +313,9 @@ struct FusedMonteCarlo : public torch::autograd::Function<FusedMonteCarlo> {
     variable_list out(23);
     const Tensor g_logw_in = grads[2], g_ci = grads[4];
     if (!g_logw_in.defined() && !g_ci.defined()) return out;
-    const auto vers = ctx->saved_data["versions"].toIntVector();
-    const Tensor gx3d0 = ctx->saved_data["guard_x3d"].toTensor();
-    ProblemTensors pt;
-    pt.x3d = ctx->saved_data["x3d"].toTensor(); pt.x2d = ctx->saved_data["x2d"].toTensor();
-    pt.w2d = ctx->saved_data["w2d"].toTensor(); pt.cam = ctx->saved_data["cam"].toTensor();
-    pt.delta = ctx->saved_data["delta"].toTensor();
-    if (!ctx->saved_data["lb"].isNone()) { pt.lb = ctx->saved_data["lb"].toTensor(); pt.ub = ctx->saved_data["ub"].toTensor(); }
-    pt.z_min = ctx->saved_data["z_min"].toDouble(); pt.huber_eps = ctx->saved_data["huber_eps"].toDouble();
-    pt.dof = ctx->saved_data["dof"].toInt();
-    const bool fold = !ctx->saved_data["dstats"].isNone();
-    if (fold) { pt.dstats = ctx->saved_data["dstats"].toTensor(); pt.drel = ctx->saved_data["drel"].toDouble(); }
-    {
-      const Tensor* ts[5] = {&gx3d0, &pt.x2d, &pt.w2d, &pt.delta, &pt.cam};
-      for (int i = 0; i < 5; ++i)
-        TORCH_CHECK((int64_t)ts[i]->_version() == vers[i],
-                    "one of the variables needed for gradient computation has been modified by an inplace operation "
-                    "(EPro-PnP recomputes its backward from x3d / x2d / w2d / delta / cam_mats: they must stay unchanged "
-                    "between forward and backward)");
-    }
+    const ProblemTensors pt = load_problem(ctx);
+    const bool fold = pt.dstats.defined();
+    check_unmodified(ctx, pt);
     const auto saved = ctx->get_saved_variables();
     const Tensor samples_n = saved[0], costs = saved[1];
     const epropnp_problem q = pt.c();
@@ -322,11 +345,7 @@ struct GnStep : public torch::autograd::Function<GnStep> {
                         double z_min, double huber_eps, int64_t dof, const Tensor& pose, double eps, bool with_plus,
                         int64_t stream, const OptTensor& delta_stats, double delta_rel) {
     (void)x3d; (void)x2d; (void)w2d;
-    ProblemTensors pt;
-    pt.x3d = x3d_c; pt.x2d = x2d_c; pt.w2d = w2d_c; pt.cam = cam_c; pt.delta = delta_c;
-    if (lb_c.has_value() && ub_c.has_value()) { pt.lb = *lb_c; pt.ub = *ub_c; }
-    if (status.has_value()) pt.status = *status;
-    pt.z_min = z_min; pt.huber_eps = huber_eps; pt.dof = dof;
+    ProblemTensors pt = problem_tensors(x3d_c, x2d_c, w2d_c, cam_c, lb_c, ub_c, delta_c, status, z_min, huber_eps, dof);
     const epropnp_problem prob = pt.c();
     const Tensor ps = pose.detach().contiguous();
     const int64_t B = prob.num_obj;
@@ -334,41 +353,18 @@ struct GnStep : public torch::autograd::Function<GnStep> {
     check(with_plus ? epropnp_pose_opt_plus_forward(&prob, (float)eps, fptr(ps), fptr(out), (void*)stream)
                     : epropnp_gn_step_forward(&prob, (float)eps, fptr(ps), fptr(out), (void*)stream), "epropnp_gn_step_forward");
     ctx->save_for_backward({ps});
-    ctx->saved_data["x3d"] = x3d_c; ctx->saved_data["x2d"] = x2d_c; ctx->saved_data["w2d"] = w2d_c;
-    ctx->saved_data["cam"] = cam_c; ctx->saved_data["delta"] = delta_c;
-    ctx->saved_data["lb"] = pt.lb.defined() ? c10::IValue(pt.lb) : c10::IValue();
-    ctx->saved_data["ub"] = pt.ub.defined() ? c10::IValue(pt.ub) : c10::IValue();
-    ctx->saved_data["z_min"] = z_min; ctx->saved_data["huber_eps"] = huber_eps; ctx->saved_data["dof"] = dof;
+    save_problem(ctx, pt, x3d_c, delta_stats, delta_rel);
     ctx->saved_data["eps"] = eps; ctx->saved_data["with_plus"] = with_plus; ctx->saved_data["stream"] = stream;
-    const bool fold = delta_stats.has_value() && delta_stats->defined();     // epropnp_problem.delta_stats: see FusedMonteCarlo
-    ctx->saved_data["dstats"] = fold ? c10::IValue(delta_stats->detach().contiguous()) : c10::IValue();
-    ctx->saved_data["drel"] = delta_rel;
     ctx->saved_data["delta_dim"] = (delta.has_value() && delta->defined()) ? (int64_t)delta->dim() : (int64_t)-1;
-    std::vector<int64_t> vers;
-    for (const Tensor* t : {&x3d_c, &x2d_c, &w2d_c, &delta_c, &cam_c}) vers.push_back((int64_t)t->_version());
-    ctx->saved_data["versions"] = vers;
     ctx->set_materialize_grads(false);
     return out;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     variable_list out(21);
     if (!grads[0].defined()) return out;
-    ProblemTensors pt;
-    pt.x3d = ctx->saved_data["x3d"].toTensor(); pt.x2d = ctx->saved_data["x2d"].toTensor();
-    pt.w2d = ctx->saved_data["w2d"].toTensor(); pt.cam = ctx->saved_data["cam"].toTensor();
-    pt.delta = ctx->saved_data["delta"].toTensor();
-    if (!ctx->saved_data["lb"].isNone()) { pt.lb = ctx->saved_data["lb"].toTensor(); pt.ub = ctx->saved_data["ub"].toTensor(); }
-    pt.z_min = ctx->saved_data["z_min"].toDouble(); pt.huber_eps = ctx->saved_data["huber_eps"].toDouble();
-    const bool fold = !ctx->saved_data["dstats"].isNone();
-    if (fold) { pt.dstats = ctx->saved_data["dstats"].toTensor(); pt.drel = ctx->saved_data["drel"].toDouble(); }
-    pt.dof = ctx->saved_data["dof"].toInt();
-    const auto vers = ctx->saved_data["versions"].toIntVector();
-    const Tensor* ts[5] = {&pt.x3d, &pt.x2d, &pt.w2d, &pt.delta, &pt.cam};
-    for (int i = 0; i < 5; ++i)
-      TORCH_CHECK((int64_t)ts[i]->_version() == vers[i],
-                  "one of the variables needed for gradient computation has been modified by an inplace operation "
-                  "(EPro-PnP recomputes its backward from x3d / x2d / w2d / delta / cam_mats: they must stay unchanged "
-                  "between forward and backward)");
+    const ProblemTensors pt = load_problem(ctx);
+    const bool fold = pt.dstats.defined();
+    check_unmodified(ctx, pt);
     const epropnp_problem q = pt.c();
     const Tensor ps = ctx->get_saved_variables()[0], g = grads[0].contiguous();
     const int64_t B = q.num_obj, N = q.num_pts;

@@ -15,7 +15,6 @@ _IN_TREE = os.path.join(os.path.dirname(_HERE), 'lib', 'libepropnp_hip.so')
 _INSTALLED = os.path.join(_HERE, '_lib', 'libepropnp_hip.so')
 LIB_PATH = os.environ.get('EPROPNP_LIB') or (_INSTALLED if (os.path.exists(_INSTALLED) and not os.path.exists(_IN_TREE)) else _IN_TREE)
 
-_f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
 
 
@@ -74,143 +73,112 @@ ABI_VERSION = 7
 _lib = None
 
 
+# Every function of include/epropnp_hip.h, in header order: 'return type: one token per parameter'.  The one place the binding
+# states a signature; tests/test_c_abi.py parses the header and compares it with this table, token by token.
+#   p  pointer (void*, float*, int32_t*, ... : device or host memory)      s  const char*
+#   i  int / int32_t     l  int64_t     u  uint64_t     z  size_t     f  float     d  double
+#   problem* lm* amis* mc* diag*  pointer to that ABI struct                i* (return) int32_t* that Python indexes
+SIGNATURES = {
+    'epropnp_amis_forward_split_bytes': 'u: problem* i i',
+    'epropnp_plan_amis_forward': 'i: problem* i i i i p',
+    'epropnp_plan_amis_backward': 'i: problem* i i i i p',
+    'epropnp_plan_evaluate_cost': 'i: problem* i p',
+    'epropnp_monte_carlo_forward': 'i: problem* mc* p p p p p p p p p p p p p p p p',
+    'epropnp_monte_carlo_forward_diag': 'i: problem* mc* p p p p p p p p p p p p p p p diag* p',
+    'epropnp_weight_stats': 'i: p i i i p p',
+    'epropnp_posterior_summary': 'i: p p p i i i p p',
+    'epropnp_posterior_resample': 'i: p p i i i i p u u p p p',
+    'epropnp_posterior_modes': 'i: p p p i i i f i p p p p p p p p',
+    'epropnp_pose_errors': 'i: p p i i i p p i p p p p p z p p',
+    'epropnp_pose_errors_scratch_bytes': 'z: i i i',
+    'epropnp_bev_overlap': 'i: p i p i i i p p',
+    'epropnp_bev_nms_scratch_bytes': 'z: i',
+    'epropnp_bev_nms': 'i: p p p i f p z p p p p',
+    'epropnp_box_overlap': 'i: p i p i i i i f i i p p',
+    'epropnp_box_overlap_plan': 'i: p p i p l p p',
+    'epropnp_box_overlap_segmented': 'i: p i p i i i i f i p i p l p',
+    'epropnp_kitti_match_scratch_bytes': 'z: i i',
+    'epropnp_kitti_match': 'i: p i l p p p i p i i p p p i p z p p p p',
+    'epropnp_kitti_thresholds': 'i: p p p i i d p p p',
+    'epropnp_kitti_statistics_scratch_bytes': 'z: i i i i',
+    'epropnp_kitti_statistics': 'i: p i l p p p p i p p p i i i p p p i p p i i p z p p p',
+    'epropnp_orient_density_scratch_bytes': 'z: i i',
+    'epropnp_orient_density': 'i: p p p i i i i i i f f f p z p p p p p',
+    'epropnp_bev_density_scratch_bytes': 'z: i i',
+    'epropnp_bev_density': 'i: p p p p i i i i i i f i i i p z p p p',
+    'epropnp_volume_centers_scratch_bytes': 'z: i i i',
+    'epropnp_volume_centers': 'i: p p p p p p i i i i i i i i i f f i p z p p p p',
+    'epropnp_box_thickness': 'i: p p p i i i i i i f p z p p p',
+    'epropnp_point_targets': 'i: p p p p p p i p p p p i i i i f p p p p p p',
+    'epropnp_obj_sample_weights': 'i: p p p l p i i f p p p p p',
+    'epropnp_abi_version': 'i:',
+    'epropnp_last_error': 's:',
+    'epropnp_profile_enable': 'i: i',
+    'epropnp_profile_reset': 'i:',
+    'epropnp_profile_read': 'i: s p p',
+    'epropnp_async_status': 'i: p i',
+    'epropnp_async_status_word': 'i*:',
+    'epropnp_noise_stride': 'i: i',
+    'epropnp_evaluate_cost': 'i: problem* p i p p',
+    'epropnp_cost_pose_cam_grad': 'i: problem* p p i i p p p',
+    'epropnp_normal_equations': 'i: problem* p i p p p p',
+    'epropnp_lm_solve': 'i: problem* lm* p p p p p p u p',
+    'epropnp_lm_solve_split_bytes': 'u: problem* lm*',
+    'epropnp_amis_forward': 'i: problem* amis* p p p p p p p',
+    'epropnp_amis_backward': 'i: problem* p p i p p p p p p p',
+    'epropnp_amis_backward_split': 'i: problem* p p i p p i p p p p p',
+    'epropnp_amis_forward_costs': 'i: problem* amis* p p p p p p p p',
+    'epropnp_monte_carlo_forward_costs': 'i: problem* mc* p p p p p p p p p p p p p p p diag* p p',
+    'epropnp_request_sample_costs': 'i: p',
+    'epropnp_amis_backward_costs': 'i: problem* p p i p p p p p p p p p',
+    'epropnp_amis_backward_split_costs': 'i: problem* p p i p p i p p p p p p p',
+    'epropnp_adaptive_delta': 'i: p p i i f p p p',
+    'epropnp_mc_loss_forward': 'i: p p i i p p p',
+    'epropnp_mc_loss_backward': 'i: p p p p i i p p p',
+    'epropnp_mc_loss_reduce': 'i: p p i f f p i l p p p',
+    'epropnp_exchange_pack': 'i: p u p i p u f p i p p',
+    'epropnp_mc_loss_reduce_backward': 'i: p p p p p i i p p p',
+    'epropnp_gn_step_forward': 'i: problem* f p p p',
+    'epropnp_gn_step_backward': 'i: problem* f p p p p p p p',
+    'epropnp_pose_opt_plus_forward': 'i: problem* f p p p',
+    'epropnp_pose_opt_plus_backward': 'i: problem* f p p p p p p p',
+    'epropnp_rslm_draw': 'i: p i i i i u u p p',
+    'epropnp_center_points': 'i: p i i p p p',
+    'epropnp_shift_poses': 'i: p p i i i f p p',
+    'epropnp_prepare_forward': 'i: p p p p i i i p p p p',
+    'epropnp_prepare_backward': 'i: p p p p p p p i i i p p p p p',
+    'epropnp_prepare_dense_forward': 'i: p p p p p p i i i i i p p p p p',
+    'epropnp_prepare_dense_backward': 'i: p p p p p p p p i i i i i p p p p p',
+    'epropnp_deform_sample_forward': 'i: p p p p p p p i i i i i i i i l l l l p p p p p p p',
+    'epropnp_deform_sample_backward': 'i: p p p p p p p p p p p p p i i i i i i i i l l l l p p p p p',
+    'epropnp_roi_logsumexp_forward': 'i: p p i i i i p p',
+    'epropnp_roi_logsumexp_backward': 'i: p p p p i i i i p p',
+    'epropnp_roi_align_forward': 'i: p p p i i i i i i i f i i l l l l l l l l p p p',
+    'epropnp_roi_align_backward': 'i: p p p i i i i i i i f i i l l l l l l l l p p p',
+    'epropnp_shift_poses_backward': 'i: p p p i i i f p p',
+    'epropnp_rslm_solve': 'i: problem* lm* i i u u p p p p p p u p',
+    'epropnp_rslm_solve_scratch_bytes': 'u: problem* i',
+    'epropnp_rslm_solve_diag': 'i: problem* lm* i i u u p p p p p p u p p',
+}
+EXPORTS = tuple(SIGNATURES)
+CTYPES = {'p': C.c_void_p, 's': C.c_char_p, 'i': C.c_int32, 'l': C.c_int64, 'u': C.c_uint64, 'z': C.c_size_t, 'f': C.c_float,
+          'd': C.c_double, 'i*': _i32p, 'problem*': C.POINTER(Problem), 'lm*': C.POINTER(LmParams), 'amis*': C.POINTER(AmisParams),
+          'mc*': C.POINTER(McParams), 'diag*': C.POINTER(Diag)}
+
+
+def signature(name, table=SIGNATURES):
+    """-> (return token, [parameter tokens]) of one table entry"""
+    ret, _, params = table[name].partition(':')
+    return ret, params.split()
+
+
 def _declare(lib):
-    vp, i32 = C.c_void_p, C.c_int32
-    lib.epropnp_abi_version.restype = C.c_int
-    lib.epropnp_last_error.restype = C.c_char_p
-    lib.epropnp_noise_stride.argtypes = [C.c_int]
-    lib.epropnp_profile_enable.argtypes = [C.c_int]
-    lib.epropnp_amis_forward_split_bytes.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32]
-    lib.epropnp_amis_forward_split_bytes.restype = C.c_uint64
-    lib.epropnp_plan_amis_forward.argtypes = [C.POINTER(Problem), i32, i32, i32, i32, C.POINTER(i32)]
-    lib.epropnp_plan_amis_backward.argtypes = [C.POINTER(Problem), i32, i32, i32, i32, C.POINTER(i32)]
-    lib.epropnp_plan_evaluate_cost.argtypes = [C.POINTER(Problem), i32, C.POINTER(i32)]
-    lib.epropnp_async_status.argtypes = [C.POINTER(C.c_int32), C.c_int]
-    lib.epropnp_async_status.restype = C.c_int
-    lib.epropnp_async_status_word.restype = C.POINTER(C.c_int32)
-    lib.epropnp_profile_read.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    lib.epropnp_monte_carlo_forward.argtypes = [C.POINTER(Problem), C.POINTER(McParams)] + [vp] * 16
-    lib.epropnp_monte_carlo_forward_diag.argtypes = [C.POINTER(Problem), C.POINTER(McParams)] + [vp] * 15 + [C.POINTER(Diag), vp]
-    lib.epropnp_weight_stats.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.epropnp_posterior_summary.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
-    lib.epropnp_posterior_resample.argtypes = [vp, vp, i32, i32, i32, i32, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
-    lib.epropnp_posterior_modes.argtypes = [vp, vp, vp, i32, i32, i32, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.epropnp_pose_errors.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
-    lib.epropnp_pose_errors_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.epropnp_pose_errors_scratch_bytes.restype = C.c_size_t
-    lib.epropnp_bev_overlap.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
-    lib.epropnp_bev_nms.argtypes = [vp, vp, vp, i32, C.c_float, vp, C.c_size_t, vp, vp, vp, vp]
-    lib.epropnp_bev_nms_scratch_bytes.argtypes = [i32]
-    lib.epropnp_bev_nms_scratch_bytes.restype = C.c_size_t
-    f32 = C.c_float
-    lib.epropnp_box_overlap.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp]
-    lib.epropnp_box_overlap_plan.argtypes = [vp, vp, i32, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.epropnp_box_overlap_segmented.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, i32, vp, i32, vp, C.c_int64, vp]
-    f64, sz = C.c_double, C.c_size_t
-    lib.epropnp_kitti_match.argtypes = [vp, i32, C.c_int64, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp]
-    lib.epropnp_kitti_thresholds.argtypes = [vp, vp, vp, i32, i32, f64, vp, vp, vp]
-    lib.epropnp_kitti_statistics.argtypes = [vp, i32, C.c_int64] + [vp] * 4 + [i32] + [vp] * 3 + [i32] * 3 + [vp] * 3 + [i32, vp, vp, i32, i32, vp, sz, vp, vp, vp]
-    lib.epropnp_kitti_match_scratch_bytes.argtypes = [i32, i32]
-    lib.epropnp_kitti_match_scratch_bytes.restype = sz
-    lib.epropnp_kitti_statistics_scratch_bytes.argtypes = [i32, i32, i32, i32]
-    lib.epropnp_kitti_statistics_scratch_bytes.restype = sz
-    lib.epropnp_orient_density.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, C.c_size_t, vp, vp, vp, vp, vp]
-    lib.epropnp_bev_density.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
-    for name in ('orient', 'bev'):
-        getattr(lib, f'epropnp_{name}_density_scratch_bytes').argtypes = [i32, i32]
-        getattr(lib, f'epropnp_{name}_density_scratch_bytes').restype = C.c_size_t
-    lib.epropnp_volume_centers.argtypes = [vp] * 6 + [i32] * 9 + [f32, f32, i32, vp, sz, vp, vp, vp, vp]
-    lib.epropnp_box_thickness.argtypes = [vp] * 3 + [i32] * 6 + [f32, vp, sz, vp, vp, vp]
-    lib.epropnp_volume_centers_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.epropnp_volume_centers_scratch_bytes.restype = sz
-    i64 = C.c_int64
-    lib.epropnp_point_targets.argtypes = [vp] * 6 + [i32] + [vp] * 4 + [i32] * 4 + [f32] + [vp] * 6
-    lib.epropnp_obj_sample_weights.argtypes = [vp] * 3 + [i64, vp, i32, i32, f32] + [vp] * 5
-    lib.epropnp_deform_sample_forward.argtypes = [vp] * 7 + [i32] * 8 + [i64] * 4 + [vp] * 7
-    lib.epropnp_deform_sample_backward.argtypes = [vp] * 13 + [i32] * 8 + [i64] * 4 + [vp] * 5
-    lib.epropnp_roi_logsumexp_forward.argtypes = [vp] * 2 + [i32] * 4 + [vp] * 2
-    lib.epropnp_roi_logsumexp_backward.argtypes = [vp] * 4 + [i32] * 4 + [vp] * 2
-    lib.epropnp_roi_align_forward.argtypes = [vp] * 3 + [i32] * 7 + [f32] + [i32] * 2 + [i64] * 8 + [vp] * 3
-    lib.epropnp_roi_align_backward.argtypes = [vp] * 3 + [i32] * 7 + [f32] + [i32] * 2 + [i64] * 8 + [vp] * 3
-    lib.epropnp_evaluate_cost.argtypes = [C.POINTER(Problem), vp, i32, vp, vp]
-    lib.epropnp_normal_equations.argtypes = [C.POINTER(Problem), vp, i32, vp, vp, vp, vp]
-    lib.epropnp_cost_pose_cam_grad.argtypes = [C.POINTER(Problem), vp, vp, i32, i32, vp, vp, vp]
-    lib.epropnp_lm_solve.argtypes = [C.POINTER(Problem), C.POINTER(LmParams), vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
-    lib.epropnp_lm_solve_split_bytes.argtypes = [C.POINTER(Problem), C.POINTER(LmParams)]
-    lib.epropnp_lm_solve_split_bytes.restype = C.c_uint64
-    lib.epropnp_amis_forward.argtypes = [C.POINTER(Problem), C.POINTER(AmisParams), vp, vp, vp, vp, vp, vp, vp]
-    lib.epropnp_amis_backward.argtypes = [C.POINTER(Problem), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.epropnp_amis_backward_split.argtypes = [C.POINTER(Problem), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
-    # the same entries with the samples' Huber costs as one more output / input (include/epropnp_hip.h: the threshold's gradient
-    # from the forward's sample costs)
-    lib.epropnp_amis_forward_costs.argtypes = [C.POINTER(Problem), C.POINTER(AmisParams), vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.epropnp_monte_carlo_forward_costs.argtypes = [C.POINTER(Problem), C.POINTER(McParams)] + [vp] * 15 + [C.POINTER(Diag), vp, vp]
-    lib.epropnp_request_sample_costs.argtypes = [vp]
-    lib.epropnp_amis_backward_costs.argtypes = [C.POINTER(Problem), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.epropnp_amis_backward_split_costs.argtypes = [C.POINTER(Problem), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.epropnp_gn_step_forward.argtypes = [C.POINTER(Problem), C.c_float, vp, vp, vp]
-    lib.epropnp_gn_step_backward.argtypes = [C.POINTER(Problem), C.c_float, vp, vp, vp, vp, vp, vp, vp]
-    lib.epropnp_pose_opt_plus_forward.argtypes = [C.POINTER(Problem), C.c_float, vp, vp, vp]
-    lib.epropnp_pose_opt_plus_backward.argtypes = [C.POINTER(Problem), C.c_float, vp, vp, vp, vp, vp, vp, vp]
-    lib.epropnp_rslm_draw.argtypes = [vp, i32, i32, i32, i32, C.c_uint64, C.c_uint64, vp, vp]
-    lib.epropnp_center_points.argtypes = [vp, i32, i32, vp, vp, vp]
-    lib.epropnp_shift_poses.argtypes = [vp, vp, i32, i32, i32, C.c_float, vp, vp]
-    lib.epropnp_shift_poses_backward.argtypes = [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp]
-    lib.epropnp_prepare_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
-    lib.epropnp_prepare_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.epropnp_prepare_dense_forward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.epropnp_prepare_dense_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.epropnp_rslm_solve.argtypes = [C.POINTER(Problem), C.POINTER(LmParams), i32, i32, C.c_uint64, C.c_uint64, vp, vp, vp,
-                                       vp, vp, vp, C.c_uint64, vp]
-    lib.epropnp_rslm_solve_diag.argtypes = [C.POINTER(Problem), C.POINTER(LmParams), i32, i32, C.c_uint64, C.c_uint64, vp, vp, vp,
-                                            vp, vp, vp, C.c_uint64, vp, vp]
-    lib.epropnp_rslm_solve_scratch_bytes.argtypes = [C.POINTER(Problem), i32]
-    lib.epropnp_rslm_solve_scratch_bytes.restype = C.c_uint64
-    lib.epropnp_adaptive_delta.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp]
-    lib.epropnp_mc_loss_forward.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    lib.epropnp_mc_loss_backward.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
-    lib.epropnp_mc_loss_reduce.argtypes = [vp, vp, i32, C.c_float, C.c_float, vp, i32, C.c_int64, vp, vp, vp]
-    lib.epropnp_exchange_pack.argtypes = [vp, C.c_uint64, vp, i32, vp, C.c_uint64, C.c_float, vp, i32, vp, vp]
-    lib.epropnp_mc_loss_reduce_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
-    for name in ('evaluate_cost', 'normal_equations', 'lm_solve', 'amis_forward', 'amis_backward', 'adaptive_delta',
-                 'mc_loss_forward', 'mc_loss_backward', 'rslm_draw', 'gn_step_forward', 'gn_step_backward', 'rslm_solve', 'center_points', 'shift_poses', 'prepare_forward', 'prepare_backward', 'pose_opt_plus_forward', 'pose_opt_plus_backward', 'shift_poses_backward', 'prepare_dense_forward',
-                 'prepare_dense_backward', 'amis_backward_split', 'monte_carlo_forward', 'cost_pose_cam_grad', 'mc_loss_reduce',
-                 'mc_loss_reduce_backward', 'plan_amis_forward', 'plan_amis_backward', 'plan_evaluate_cost',
-                 'monte_carlo_forward_diag', 'weight_stats', 'rslm_solve_diag', 'posterior_summary', 'posterior_resample',
-                 'posterior_modes', 'amis_forward_costs', 'monte_carlo_forward_costs', 'amis_backward_costs',
-                 'amis_backward_split_costs', 'request_sample_costs', 'pose_errors', 'bev_overlap', 'bev_nms', 'orient_density',
-                 'bev_density', 'deform_sample_forward', 'deform_sample_backward', 'roi_logsumexp_forward',
-                 'roi_logsumexp_backward', 'roi_align_forward', 'roi_align_backward', 'box_overlap', 'box_overlap_plan',
-                 'box_overlap_segmented', 'kitti_match', 'kitti_thresholds', 'kitti_statistics', 'volume_centers', 'box_thickness',
-                 'point_targets', 'obj_sample_weights'):
-        getattr(lib, 'epropnp_' + name).restype = C.c_int
+    """Give every exported function of a loaded library its argtypes and restype from SIGNATURES."""
+    for name in SIGNATURES:
+        ret, params = signature(name)
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = CTYPES[ret], [CTYPES[t] for t in params]
     return lib
-
-
-EXPORTS = ('epropnp_abi_version', 'epropnp_last_error', 'epropnp_noise_stride', 'epropnp_profile_enable',
-           'epropnp_profile_reset', 'epropnp_profile_read', 'epropnp_evaluate_cost',
-           'epropnp_normal_equations', 'epropnp_lm_solve', 'epropnp_amis_forward', 'epropnp_amis_backward',
-           'epropnp_adaptive_delta', 'epropnp_mc_loss_forward', 'epropnp_mc_loss_backward', 'epropnp_rslm_draw',
-           'epropnp_gn_step_forward', 'epropnp_gn_step_backward', 'epropnp_rslm_solve',
-           'epropnp_center_points', 'epropnp_shift_poses', 'epropnp_prepare_forward', 'epropnp_prepare_backward',
-           'epropnp_pose_opt_plus_forward', 'epropnp_pose_opt_plus_backward', 'epropnp_shift_poses_backward',
-           'epropnp_prepare_dense_forward', 'epropnp_prepare_dense_backward', 'epropnp_amis_backward_split',
-           'epropnp_monte_carlo_forward', 'epropnp_cost_pose_cam_grad', 'epropnp_async_status',
-           'epropnp_async_status_word', 'epropnp_amis_forward_split_bytes', 'epropnp_rslm_solve_scratch_bytes',
-           'epropnp_lm_solve_split_bytes', 'epropnp_mc_loss_reduce', 'epropnp_mc_loss_reduce_backward', 'epropnp_exchange_pack',
-           'epropnp_plan_amis_forward', 'epropnp_plan_amis_backward', 'epropnp_plan_evaluate_cost',
-           'epropnp_monte_carlo_forward_diag', 'epropnp_weight_stats', 'epropnp_rslm_solve_diag',
-           'epropnp_posterior_summary', 'epropnp_posterior_resample', 'epropnp_posterior_modes',
-           'epropnp_amis_forward_costs', 'epropnp_monte_carlo_forward_costs', 'epropnp_amis_backward_costs',
-           'epropnp_amis_backward_split_costs', 'epropnp_request_sample_costs', 'epropnp_pose_errors',
-           'epropnp_pose_errors_scratch_bytes', 'epropnp_bev_overlap', 'epropnp_bev_nms', 'epropnp_bev_nms_scratch_bytes',
-           'epropnp_orient_density', 'epropnp_orient_density_scratch_bytes', 'epropnp_bev_density',
-           'epropnp_bev_density_scratch_bytes', 'epropnp_deform_sample_forward', 'epropnp_deform_sample_backward',
-           'epropnp_roi_logsumexp_forward', 'epropnp_roi_logsumexp_backward', 'epropnp_roi_align_forward',
-           'epropnp_roi_align_backward', 'epropnp_box_overlap', 'epropnp_box_overlap_plan', 'epropnp_box_overlap_segmented',
-           'epropnp_kitti_match', 'epropnp_kitti_match_scratch_bytes', 'epropnp_kitti_thresholds', 'epropnp_kitti_statistics',
-           'epropnp_kitti_statistics_scratch_bytes', 'epropnp_volume_centers', 'epropnp_volume_centers_scratch_bytes',
-           'epropnp_box_thickness', 'epropnp_point_targets', 'epropnp_obj_sample_weights')
 
 
 def lib():

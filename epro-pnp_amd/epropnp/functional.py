@@ -144,8 +144,8 @@ class diagnostics:
             out = layer.monte_carlo_forward(x3d, x2d, w2d, camera, cost_fun, pose_init=...)
         rec = diag.records[-1]
 
-    The outputs and gradients of the calls are bit-identical to those outside the block; the fused forward goes through
-    epropnp_monte_carlo_forward_diag (one more small launch for the weight statistics).  Outside a block nothing changes.  Not
+    The outputs and gradients of the calls are bit-identical to those outside the block; the fused forward hands
+    epropnp_monte_carlo_forward_costs an epropnp_diag (one more small launch for the weight statistics).  Outside a block nothing changes.  Not
     supported inside a hipGraph capture: calls made while the stream captures, and GraphedLoss, record nothing."""
 
     def __init__(self):
@@ -273,10 +273,22 @@ class PnPProblem:
         return other
 
 
-def _guard_inputs(ctx, prob):
+def _guard_inputs(ctx, prob, delta=None):
     """Remember the version counters of the tensors the recompute backward will read again (the nodes keep raw device
-    pointers, not autograd-saved tensors, so autograd's own in-place check does not see them)."""
+    pointers, not autograd-saved tensors, so autograd's own in-place check does not see them), and the shape of the node's
+    `delta` input for `_correspondence_grads`."""
     ctx.guarded = [(t, t._version) for t in (prob.x3d, prob.x2d, prob.w2d, prob.delta, prob.cam)]
+    ctx.delta_shape = delta.shape if isinstance(delta, torch.Tensor) else None
+
+
+def _correspondence_grads(ctx, gx3d, gx2d, gw2d, gdel):
+    """The backward's return tuple of a node whose inputs are (x3d, x2d, w2d, delta, non-tensors ...): each gradient only
+    where it is needed, the per-object (B,) threshold gradient in the shape of the node's delta."""
+    need = ctx.needs_input_grad
+    gdelta = None
+    if ctx.delta_shape is not None and need[3]:
+        gdelta = gdel.sum() if len(ctx.delta_shape) == 0 else gdel.reshape(ctx.delta_shape)
+    return (gx3d if need[0] else None, gx2d if need[1] else None, gw2d if need[2] else None, gdelta) + (None,) * (len(need) - 4)
 
 
 def _check_inputs(ctx):
@@ -484,13 +496,9 @@ def amis_forward(prob, pose_opt, pose_cov, mc_samples, num_iter, eps=1e-5, acg_m
         nz = _f32c(noise, 'noise')
         assert nz.shape == (B, num_iter, S // num_iter, noise_stride(prob.dof)), f'noise shape {tuple(nz.shape)}'
     par, scratch = _amis_struct(prob, S, num_iter, eps, acg_mle_iter, acg_dispersion, seed, offset, offset_dev)
-    costs = prob.new(S, B) if with_costs else None
-    if with_costs:
-        _hip.call('epropnp_amis_forward_costs', C.byref(prob.c), C.byref(par), _hip.ptr(po), _hip.ptr(pc), _hip.ptr(nz),
-                  _hip.ptr(samples), _hip.ptr(logw), _hip.ptr(props), _hip.ptr(costs), prob.stream)
-    else:
-        _hip.call('epropnp_amis_forward', C.byref(prob.c), C.byref(par), _hip.ptr(po), _hip.ptr(pc), _hip.ptr(nz),
-                  _hip.ptr(samples), _hip.ptr(logw), _hip.ptr(props), prob.stream)
+    costs = prob.new(S, B) if with_costs else None      # (NULL: the entry without costs, bit for bit)
+    _hip.call('epropnp_amis_forward_costs', C.byref(prob.c), C.byref(par), _hip.ptr(po), _hip.ptr(pc), _hip.ptr(nz),
+              _hip.ptr(samples), _hip.ptr(logw), _hip.ptr(props), _hip.ptr(costs), prob.stream)
     del scratch          # stream-ordered reuse by the caching allocator: the launch is enqueued
     return (samples, logw) + ((props,) if with_proposals else ()) + ((costs,) if with_costs else ())
 
@@ -597,23 +605,16 @@ def amis_backward(prob, pose_samples, grad_logweights, pose_init=None, grad_cost
             cin = _f32c(cost_init, 'cost_init')
             if cin.numel() != B:
                 raise ValueError(f'cost_init must hold num_obj = {B} values, got {tuple(cin.shape)}')
+    # (costs NULL: the entries without costs, bit for bit -- the per-pair term)
     if nsplit > 1:
         parts = prob.new(B, nsplit)
-        if costs is None:
-            _hip.call('epropnp_amis_backward_split', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin),
-                      _hip.ptr(gin), nsplit, _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(parts), prob.stream)
-        else:
-            _hip.call('epropnp_amis_backward_split_costs', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin),
-                      _hip.ptr(gin), nsplit, _hip.ptr(costs), _hip.ptr(cin), _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d),
-                      _hip.ptr(parts), prob.stream)
+        _hip.call('epropnp_amis_backward_split_costs', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin),
+                  _hip.ptr(gin), nsplit, _hip.ptr(costs), _hip.ptr(cin), _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d),
+                  _hip.ptr(parts), prob.stream)
         return gx3d, gx2d, gw2d, parts.sum(dim=1)
     gdel = prob.new(B)
-    if costs is None:
-        _hip.call('epropnp_amis_backward', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin), _hip.ptr(gin),
-                  _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(gdel), prob.stream)
-    else:
-        _hip.call('epropnp_amis_backward_costs', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin), _hip.ptr(gin),
-                  _hip.ptr(costs), _hip.ptr(cin), _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(gdel), prob.stream)
+    _hip.call('epropnp_amis_backward_costs', C.byref(cs), _hip.ptr(smp), _hip.ptr(glw), S, _hip.ptr(pin), _hip.ptr(gin),
+              _hip.ptr(costs), _hip.ptr(cin), _hip.ptr(gx3d), _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(gdel), prob.stream)
     return gx3d, gx2d, gw2d, gdel
 
 
@@ -629,11 +630,10 @@ class _MonteCarloCost(torch.autograd.Function):
         samples, logw, costs = amis_forward(prob, pose_opt, pose_cov, with_costs=True, **cfg)
         ctx.set_materialize_grads(False)      # no (S,B,7) zero tensor for the non-differentiable samples output
         ctx.prob, ctx.pose_init = prob, pose_init
-        _guard_inputs(ctx, prob)
+        _guard_inputs(ctx, prob, delta)
         # (the samples' costs and the cost of pose_init: the threshold's gradient, amis_backward)
         ctx.save_for_backward(samples, costs, None if cost_init_value is None else cost_init_value.detach())
         ctx.mark_non_differentiable(samples)
-        ctx.delta_shape = delta.shape if isinstance(delta, torch.Tensor) else None
         if cost_init_value is None:
             return samples, logw
         return samples, logw, cost_init_value.clone()
@@ -649,11 +649,7 @@ class _MonteCarloCost(torch.autograd.Function):
             g_logw = torch.full(samples.shape[:2], 0.0, dtype=torch.float32, device=samples.device)
         gx3d, gx2d, gw2d, gdel = amis_backward(prob, samples, g_logw, ctx.pose_init, g_cost_init, sample_costs=costs,
                                                cost_init=cost_init)
-        gdelta = None
-        if ctx.delta_shape is not None and ctx.needs_input_grad[3]:
-            gdelta = gdel.sum() if len(ctx.delta_shape) == 0 else gdel.reshape(ctx.delta_shape)
-        return (gx3d if ctx.needs_input_grad[0] else None, gx2d if ctx.needs_input_grad[1] else None,
-                gw2d if ctx.needs_input_grad[2] else None, gdelta, None, None, None, None, None, None)
+        return _correspondence_grads(ctx, gx3d, gx2d, gw2d, gdel)
 
 
 def monte_carlo_cost(x3d, x2d, w2d, delta, prob, pose_opt, pose_cov, pose_init, cost_init_value, cfg):
@@ -667,7 +663,7 @@ def _lm_struct(solver, fast_mode):
 
 
 class _FusedMonteCarlo(torch.autograd.Function):
-    """monte_carlo_forward as ONE autograd node over ONE host call (epropnp_monte_carlo_forward, csrc/mc_forward.hip):
+    """monte_carlo_forward as ONE autograd node over ONE host call (epropnp_monte_carlo_forward_costs, csrc/mc_forward.hip):
     [normalize] -> cost_init -> [RSLM, cheaper-of-two start] -> LM -> AMIS -> [denormalize] are enqueued from C++;
     (x3d, x2d, w2d, delta) -> (pose_opt, cost, pose_samples, logweights, cost_init), the last two differentiable.
     Backward: the same recompute kernel as _MonteCarloCost, in the solver's (normalised) frame."""
@@ -693,19 +689,16 @@ class _FusedMonteCarlo(torch.autograd.Function):
         pose_opt, samples = (new(B, PL), new(S, B, PL)) if normalize else (None, None)     # caller's frame
         costs = new(S, B)       # the samples' Huber costs: the backward's threshold gradient (amis_backward)
         p = _hip.ptr
-        _hip.call('epropnp_request_sample_costs', p(costs))      # the forward call below writes them (include/epropnp_hip.h)
-        if diag is None:
-            _hip.call('epropnp_monte_carlo_forward', C.byref(prob.c), C.byref(par), p(pin), p(nz), p(x3d_c), p(offset), p(pin_n),
-                      p(start_pose), p(start_cost), p(pose_opt_n), p(pose_cov), p(cost), p(samples_n), p(logw), p(cost_init),
-                      p(pose_opt), p(samples), prob.stream)
-        else:       # inside a `diagnostics()` block: the same launches plus the record's tensors
+        dg = None       # (NULL: exactly the launches of the entry without diagnostics)
+        if diag is not None:       # inside a `diagnostics()` block: the same launches plus the record's tensors
             K = par.amis.num_iter
             rec = DiagRecord(None if par.lm.fast_mode else new(B, dtype=torch.int32),
                              new(B, dtype=torch.int32) if par.init_mode else None, new(B, K, 40), new(B, K + 3))
-            dg = _hip.Diag(p(rec.lm_accept_mask), p(rec.rslm_winner), p(rec.proposals), p(rec.weight_stats))
-            _hip.call('epropnp_monte_carlo_forward_diag', C.byref(prob.c), C.byref(par), p(pin), p(nz), p(x3d_c), p(offset),
-                      p(pin_n), p(start_pose), p(start_cost), p(pose_opt_n), p(pose_cov), p(cost), p(samples_n), p(logw),
-                      p(cost_init), p(pose_opt), p(samples), C.byref(dg), prob.stream)
+            dg = C.byref(_hip.Diag(p(rec.lm_accept_mask), p(rec.rslm_winner), p(rec.proposals), p(rec.weight_stats)))
+        _hip.call('epropnp_monte_carlo_forward_costs', C.byref(prob.c), C.byref(par), p(pin), p(nz), p(x3d_c), p(offset), p(pin_n),
+                  p(start_pose), p(start_cost), p(pose_opt_n), p(pose_cov), p(cost), p(samples_n), p(logw), p(cost_init),
+                  p(pose_opt), p(samples), dg, p(costs), prob.stream)
+        if diag is not None:
             diag.records.append(rec)
         if normalize:      # the backward differentiates the cost in the solver frame: same problem, centred points
             bprob = _hip.Problem.from_buffer_copy(prob.c)       # (prob.fold_delta travels with the copy)
@@ -714,9 +707,8 @@ class _FusedMonteCarlo(torch.autograd.Function):
             bprob = prob.c
         ctx.set_materialize_grads(False)
         ctx.prob, ctx.bprob, ctx.keep = prob, bprob, (x3d_c, pin_n if normalize else pin)
-        _guard_inputs(ctx, prob)
+        _guard_inputs(ctx, prob, delta)
         ctx.save_for_backward(samples_n, costs, cost_init)
-        ctx.delta_shape = delta.shape if isinstance(delta, torch.Tensor) else None
         ctx.mark_non_differentiable(*[t for t in (pose_opt_n, samples_n, cost, pose_opt, samples, x3d_c, offset) if t is not None])
         return pose_opt_n, samples_n, logw, cost, cost_init, pose_opt, samples, x3d_c, offset
 
@@ -733,11 +725,7 @@ class _FusedMonteCarlo(torch.autograd.Function):
         gx3d, gx2d, gw2d, gdel = amis_backward(prob, samples_n, g_logw, pin if g_cost_init is not None else None,
                                                g_cost_init, cstruct=ctx.bprob, sample_costs=costs,
                                                cost_init=None if cost_init is None else cost_init.detach())
-        gdelta = None
-        if ctx.delta_shape is not None and ctx.needs_input_grad[3]:
-            gdelta = gdel.sum() if len(ctx.delta_shape) == 0 else gdel.reshape(ctx.delta_shape)
-        return (gx3d if ctx.needs_input_grad[0] else None, gx2d if ctx.needs_input_grad[1] else None,
-                gw2d if ctx.needs_input_grad[2] else None, gdelta, None, None, None, None, None, None)
+        return _correspondence_grads(ctx, gx3d, gx2d, gw2d, gdel)
 
 
 def fused_monte_carlo(x3d, x2d, w2d, delta, prob, pose_init, par, noise, with_cost, diag=None):
@@ -966,16 +954,22 @@ def center_points(x3d):
     return _CenterPoints.apply(x3d)
 
 
+def _shift_poses_launch(pose, offset, sign):
+    """-> the shifted poses, and the contiguous fp32 (pose, offset) the kernel read"""
+    ps, off = _f32c(pose.detach(), 'pose'), _f32c(offset.detach(), 'offset')
+    B, pl = ps.shape[-2], ps.shape[-1]
+    out = torch.empty_like(ps)
+    _hip.call('epropnp_shift_poses', _hip.ptr(ps), _hip.ptr(off), ps.numel() // (B * pl), B, 6 if pl == 7 else 4,
+              float(sign), _hip.ptr(out), _hip.stream_of(ps))
+    return out, ps, off
+
+
 class _ShiftPoses(torch.autograd.Function):
     """pose translation += sign * R(pose) offset, differentiable w.r.t. the pose (offset is a constant)."""
 
     @staticmethod
     def forward(ctx, pose, offset, sign):
-        ps, off = _f32c(pose.detach(), 'pose'), _f32c(offset.detach(), 'offset')
-        B, pl = ps.shape[-2], ps.shape[-1]
-        out = torch.empty_like(ps)
-        _hip.call('epropnp_shift_poses', _hip.ptr(ps), _hip.ptr(off), ps.numel() // (B * pl), B, 6 if pl == 7 else 4,
-                  float(sign), _hip.ptr(out), _hip.stream_of(ps))
+        out, ps, off = _shift_poses_launch(pose, offset, sign)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(ps, off)
         ctx.sign = float(sign)
@@ -1002,12 +996,7 @@ def shift_poses(pose, offset, sign):
             _f32c(pose, 'pose'), _f32c(offset, 'offset')
             return ext.shift_poses(pose, offset, float(sign), int(_hip.stream_of(pose) or 0))
         return _ShiftPoses.apply(pose, offset, sign)
-    ps, off = _f32c(pose.detach(), 'pose'), _f32c(offset.detach(), 'offset')
-    B, pl = ps.shape[-2], ps.shape[-1]
-    out = torch.empty_like(ps)
-    _hip.call('epropnp_shift_poses', _hip.ptr(ps), _hip.ptr(off), ps.numel() // (B * pl), B, 6 if pl == 7 else 4,
-              float(sign), _hip.ptr(out), _hip.stream_of(ps))
-    return out
+    return _shift_poses_launch(pose, offset, sign)[0]
 
 
 RSLM_MAX_POINTS = 512      # epropnp_rslm_solve keeps an object's correspondences + 16 key rows in LDS
@@ -1031,16 +1020,11 @@ def rslm_solve(prob, num_proposals, num_points, num_iter, seed=0, offset=0, inds
     par = _hip.LmParams(int(num_iter), int(bool(fast_mode)), min_lm_diagonal, max_lm_diagonal, min_relative_decrease,
                         initial_trust_region_radius, max_trust_region_radius, eps)
     scratch = rslm_scratch(prob, P)
-    if with_winner:
-        winner = prob.new(prob.B, dtype=torch.int32)
-        _hip.call('epropnp_rslm_solve_diag', C.byref(prob.c), C.byref(par), P, n, int(seed), int(offset), _hip.ptr(offset_dev),
-                  _hip.ptr(inds), _hip.ptr(rot), _hip.ptr(pose), _hip.ptr(cost), _hip.ptr(scratch),
-                  0 if scratch is None else scratch.numel() * 4, _hip.ptr(winner), prob.stream)
-        return pose, cost, winner
-    _hip.call('epropnp_rslm_solve', C.byref(prob.c), C.byref(par), P, n, int(seed), int(offset), _hip.ptr(offset_dev),
+    winner = prob.new(prob.B, dtype=torch.int32) if with_winner else None      # (NULL: epropnp_rslm_solve, bit for bit)
+    _hip.call('epropnp_rslm_solve_diag', C.byref(prob.c), C.byref(par), P, n, int(seed), int(offset), _hip.ptr(offset_dev),
               _hip.ptr(inds), _hip.ptr(rot), _hip.ptr(pose), _hip.ptr(cost), _hip.ptr(scratch),
-              0 if scratch is None else scratch.numel() * 4, prob.stream)
-    return pose, cost
+              0 if scratch is None else scratch.numel() * 4, _hip.ptr(winner), prob.stream)
+    return (pose, cost, winner) if with_winner else (pose, cost)
 
 
 def rslm_scratch(prob, num_proposals):
@@ -1051,92 +1035,54 @@ def rslm_scratch(prob, num_proposals):
 
 
 class _GnStep(torch.autograd.Function):
-    """step = -(J^T J + eps I)^-1 J^T r at `pose`, differentiable w.r.t. x3d, x2d, w2d, delta (one sweep forward,
-    two sweeps backward, nothing materialised; reference: levenberg_marquardt.py:243-253 + autograd)."""
+    """step = -(J^T J + eps I)^-1 J^T r at `pose` (reference: levenberg_marquardt.py:243-253 + autograd) or, `with_plus`,
+    pose (+) step: the Gauss-Newton step and LMSolver.pose_add in one kernel each way (:70-72 -> :243-265).  Differentiable
+    w.r.t. x3d, x2d, w2d, delta: one sweep forward, two sweeps backward, nothing materialised.  The node of
+    csrc/torch_binding.cpp, over the same entry points."""
 
     @staticmethod
-    def forward(ctx, x3d, x2d, w2d, delta, prob, pose, eps):
+    def forward(ctx, x3d, x2d, w2d, delta, prob, pose, eps, with_plus):
         ps = _f32c(pose, 'pose')
-        step = prob.new(prob.B, prob.dof)
-        _hip.call('epropnp_gn_step_forward', C.byref(prob.c), float(eps), _hip.ptr(ps), _hip.ptr(step), prob.stream)
+        ctx.entry = 'epropnp_pose_opt_plus' if with_plus else 'epropnp_gn_step'
+        out = prob.new(prob.B, prob.pose_len if with_plus else prob.dof)
+        _hip.call(ctx.entry + '_forward', C.byref(prob.c), float(eps), _hip.ptr(ps), _hip.ptr(out), prob.stream)
         ctx.set_materialize_grads(False)
         ctx.prob, ctx.eps = prob, float(eps)
-        _guard_inputs(ctx, prob)
+        _guard_inputs(ctx, prob, delta)
         ctx.save_for_backward(ps)
-        ctx.delta_shape = delta.shape if isinstance(delta, torch.Tensor) else None
-        return step
+        return out
 
     @staticmethod
     def backward(ctx, g):
         if g is None:
-            return (None,) * 7
+            return (None,) * 8
         _check_inputs(ctx)
         (ps,) = ctx.saved_tensors
         prob = ctx.prob
         B, N = prob.B, prob.N
         g = g.contiguous()
         gx3d, gx2d, gw2d, gdel = prob.new(B, N, 3), prob.new(B, N, 2), prob.new(B, N, 2), prob.new(B)
-        _hip.call('epropnp_gn_step_backward', C.byref(prob.c), ctx.eps, _hip.ptr(ps), _hip.ptr(g), _hip.ptr(gx3d),
+        _hip.call(ctx.entry + '_backward', C.byref(prob.c), ctx.eps, _hip.ptr(ps), _hip.ptr(g), _hip.ptr(gx3d),
                   _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(gdel), prob.stream)
-        gdelta = None
-        if ctx.delta_shape is not None and ctx.needs_input_grad[3]:
-            gdelta = gdel.sum() if len(ctx.delta_shape) == 0 else gdel.reshape(ctx.delta_shape)
-        return (gx3d if ctx.needs_input_grad[0] else None, gx2d if ctx.needs_input_grad[1] else None,
-                gw2d if ctx.needs_input_grad[2] else None, gdelta, None, None, None)
+        return _correspondence_grads(ctx, gx3d, gx2d, gw2d, gdel)
 
 
-def _ext_gn_step(ext, x3d, x2d, w2d, delta, prob, pose, eps, with_plus):
-    _f32c(pose, 'pose')
+def _gn_step(x3d, x2d, w2d, delta, prob, pose, eps, with_plus):
     fold = prob.delta_fold
-    return ext.gn_step(x3d, x2d, w2d, None if fold else delta, prob.x3d, prob.x2d, prob.w2d, prob.cam, prob.lb, prob.ub,
-                       prob.delta, prob.status, prob.z_min, prob.huber_eps, prob.dof, pose, float(eps), with_plus,
-                       int(prob.stream or 0), None if fold is None else fold[0], 0.0 if fold is None else fold[1])
+    if fold is not None:      # the kernels add delta's gradient to grad_w2d themselves: the node returns none for delta
+        delta = None
+    ext = _hip.torch_ext()
+    if ext is None:
+        return _GnStep.apply(x3d, x2d, w2d, delta, prob, pose, eps, with_plus)
+    _f32c(pose, 'pose')
+    return ext.gn_step(x3d, x2d, w2d, delta, prob.x3d, prob.x2d, prob.w2d, prob.cam, prob.lb, prob.ub, prob.delta, prob.status,
+                       prob.z_min, prob.huber_eps, prob.dof, pose, float(eps), with_plus, int(prob.stream or 0),
+                       None if fold is None else fold[0], 0.0 if fold is None else fold[1])
 
 
 def gn_step(x3d, x2d, w2d, delta, prob, pose, eps):
-    ext = _hip.torch_ext()
-    if ext is not None:
-        return _ext_gn_step(ext, x3d, x2d, w2d, delta, prob, pose, eps, False)
-    return _GnStep.apply(x3d, x2d, w2d, None if prob.delta_fold else delta, prob, pose, eps)
-
-
-class _PoseOptPlus(torch.autograd.Function):
-    """pose_opt_plus = pose (+) gn_step(pose): the Gauss-Newton step and LMSolver.pose_add in one kernel each way
-    (reference: levenberg_marquardt.py:70-72 -> :243-265 + autograd)."""
-
-    @staticmethod
-    def forward(ctx, x3d, x2d, w2d, delta, prob, pose, eps):
-        ps = _f32c(pose, 'pose')
-        plus = prob.new(prob.B, prob.pose_len)
-        _hip.call('epropnp_pose_opt_plus_forward', C.byref(prob.c), float(eps), _hip.ptr(ps), _hip.ptr(plus), prob.stream)
-        ctx.set_materialize_grads(False)
-        ctx.prob, ctx.eps = prob, float(eps)
-        _guard_inputs(ctx, prob)
-        ctx.save_for_backward(ps)
-        ctx.delta_shape = delta.shape if isinstance(delta, torch.Tensor) else None
-        return plus
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return (None,) * 7
-        _check_inputs(ctx)
-        (ps,) = ctx.saved_tensors
-        prob = ctx.prob
-        B, N = prob.B, prob.N
-        g = g.contiguous()
-        gx3d, gx2d, gw2d, gdel = prob.new(B, N, 3), prob.new(B, N, 2), prob.new(B, N, 2), prob.new(B)
-        _hip.call('epropnp_pose_opt_plus_backward', C.byref(prob.c), ctx.eps, _hip.ptr(ps), _hip.ptr(g), _hip.ptr(gx3d),
-                  _hip.ptr(gx2d), _hip.ptr(gw2d), _hip.ptr(gdel), prob.stream)
-        gdelta = None
-        if ctx.delta_shape is not None and ctx.needs_input_grad[3]:
-            gdelta = gdel.sum() if len(ctx.delta_shape) == 0 else gdel.reshape(ctx.delta_shape)
-        return (gx3d if ctx.needs_input_grad[0] else None, gx2d if ctx.needs_input_grad[1] else None,
-                gw2d if ctx.needs_input_grad[2] else None, gdelta, None, None, None)
+    return _gn_step(x3d, x2d, w2d, delta, prob, pose, eps, False)
 
 
 def pose_opt_plus(x3d, x2d, w2d, delta, prob, pose, eps):
-    ext = _hip.torch_ext()
-    if ext is not None:
-        return _ext_gn_step(ext, x3d, x2d, w2d, delta, prob, pose, eps, True)
-    return _PoseOptPlus.apply(x3d, x2d, w2d, None if prob.delta_fold else delta, prob, pose, eps)
+    return _gn_step(x3d, x2d, w2d, delta, prob, pose, eps, True)

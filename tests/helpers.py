@@ -133,6 +133,67 @@ def rel_per_object(a, b):
     return d / b.abs().reshape(b.shape[0], -1).amax(1).clamp(min=1e-30)
 
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+
+
+def abi_lib():
+    """A private handle of the in-tree library, built first if it is missing, with every function's argtypes and restype from the
+    binding's one signature table (epropnp/_hip.py: SIGNATURES, held against the header by tests/test_c_abi.py)."""
+    import ctypes
+    if not os.path.exists(LIB):
+        import importlib.util
+        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        mod.build()
+    from epropnp import _hip
+    return _hip._declare(ctypes.CDLL(LIB))
+
+
+def check_abi_additive(lib, names):
+    """`names` are exported by the library and listed by the binding, and the ABI version stays 7 in both."""
+    from epropnp import _hip
+    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
+    for name in names:
+        assert hasattr(lib, name), f'{name} not exported'
+        assert name in _hip.EXPORTS
+
+
+def check_header_is_plain_c(tmp_path, names, facts=(), body=(), run=False):
+    """include/epropnp_hip.h with a program that takes the address of every function of `names` passes gcc -std=c99 -Wall -Wextra
+    -pedantic -Werror and g++ -std=c++11 -Wall -Werror; EPROPNP_ABI_VERSION == 7 and every C constant expression of `facts` hold
+    at compile time (an array of size -1 otherwise).  `body`: further statements of main.  run: also link the program against the
+    library, run it and return its output as a dict of the first word of each line to the second (`name 1` per function)."""
+    import shutil
+    import subprocess
+    import pytest
+    if shutil.which('gcc') is None:
+        pytest.skip('gcc not available')
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "epropnp_hip.h"']
+    lines += [f'typedef char fact_{i}[({fact}) ? 1 : -1];' for i, fact in enumerate(['EPROPNP_ABI_VERSION == 7', *facts])]
+    lines += ['int main(void) {'] + [f'  printf("{n} %d\\n", (int)(sizeof(&{n}) > 0));' for n in names]
+    lines += [f'  {stmt}' for stmt in body] + ['  return 0;', '}']
+    src = tmp_path / 'abi_entries.c'
+    src.write_text('\n'.join(lines) + '\n')
+    inc = os.path.join(ROOT, 'include')
+    for cmd in (['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror'], ['g++', '-std=c++11', '-Wall', '-Werror', '-x', 'c++']):
+        r = subprocess.run(cmd + ['-I', inc, '-fsyntax-only', str(src)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+    if not run:
+        return None
+    abi_lib()
+    exe, libdir = tmp_path / 'abi_entries', os.path.dirname(LIB)
+    r = subprocess.run(['gcc', '-std=c99', '-pedantic', '-Werror', '-I', inc, str(src), '-o', str(exe), '-L', libdir, '-lepropnp_hip',
+                        '-Wl,-rpath,' + libdir, '-Wl,-rpath,/opt/rocm/lib', '-L', '/opt/rocm/lib'], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    got = dict(line.split() for line in out.stdout.splitlines())
+    assert all(got[n] == '1' for n in names)
+    return got
+
+
 def set_tune(monkeypatch, **keys):
     """EPROPNP_TUNE (csrc/pnp_host.h: tune_value, epropnp/_hip.py: tune) from keyword arguments: `bwd_impl='valu'`, `bwd_mfma='4,2'`,
     a bare flag as `rslm_composite=True`; no keys (or only None / False values) removes the variable."""

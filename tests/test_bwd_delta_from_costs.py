@@ -151,28 +151,26 @@ def test_without_costs_the_new_entries_are_the_old_ones(backend, monkeypatch, do
     g_logw, g_init = (t.to(backend) for t in _weights('zeros'))
     ptr = _hip.ptr
 
-    def new_entry(nsplit, c, ci):
+    def entry(nsplit, *costs):
+        """the old entries (no costs arguments) / the new ones, through raw pointers"""
         gx3d, gx2d, gw2d = hp.new(B, N, 3), hp.new(B, N, 2), hp.new(B, N, 2)
-        if nsplit == 1:
-            gd = hp.new(B)
-            _hip.call('epropnp_amis_backward_costs', C.byref(hp.c), ptr(samples), ptr(g_logw), S, ptr(p['pose_init']), ptr(g_init),
-                      ptr(c), ptr(ci), ptr(gx3d), ptr(gx2d), ptr(gw2d), ptr(gd), hp.stream)
-        else:
-            parts = hp.new(B, nsplit)
-            _hip.call('epropnp_amis_backward_split_costs', C.byref(hp.c), ptr(samples), ptr(g_logw), S, ptr(p['pose_init']),
-                      ptr(g_init), nsplit, ptr(c), ptr(ci), ptr(gx3d), ptr(gx2d), ptr(gw2d), ptr(parts), hp.stream)
-            gd = parts.sum(dim=1)
-        return gx3d, gx2d, gw2d, gd
+        gd = hp.new(B) if nsplit == 1 else hp.new(B, nsplit)
+        name = ('epropnp_amis_backward' if nsplit == 1 else 'epropnp_amis_backward_split') + ('_costs' if costs else '')
+        _hip.call(name, C.byref(hp.c), ptr(samples), ptr(g_logw), S, ptr(p['pose_init']), ptr(g_init), *((nsplit,) if nsplit > 1 else ()),
+                  *(ptr(c) for c in costs), ptr(gx3d), ptr(gx2d), ptr(gw2d), ptr(gd), hp.stream)
+        return gx3d, gx2d, gw2d, gd if nsplit == 1 else gd.sum(dim=1)
 
     for nsplit in (1, 2):
-        old = F.amis_backward(hp, samples, g_logw, p['pose_init'], g_init, nsplit=nsplit)
+        old = entry(nsplit)
+        for a, b in zip(old, F.amis_backward(hp, samples, g_logw, p['pose_init'], g_init, nsplit=nsplit)):      # (the package: NULL costs)
+            assert torch.equal(a, b), nsplit
         for c, ci in ((None, None), (None, cost_init), (costs, None)):
-            for a, b in zip(old, new_entry(nsplit, c, ci)):
+            for a, b in zip(old, entry(nsplit, c, ci)):
                 assert torch.equal(a, b), (nsplit, c is None, ci is None)
-        with_costs = new_entry(nsplit, costs, cost_init)
+        with_costs = entry(nsplit, costs, cost_init)
         assert not torch.equal(with_costs[3], old[3])          # (the cost path is taken when both are there: other roundings)
         set_tune(monkeypatch, bwd_mfma='4,4', bwd_dcost=0)
-        for a, b in zip(old, new_entry(nsplit, costs, cost_init)):
+        for a, b in zip(old, entry(nsplit, costs, cost_init)):
             assert torch.equal(a, b), nsplit
         set_tune(monkeypatch, bwd_mfma='4,4')
 

@@ -7,8 +7,7 @@ import re
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import ROOT, abi_lib
 
 
 def declared_symbols():
@@ -19,13 +18,125 @@ def declared_symbols():
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    return ctypes.CDLL(LIB)
+    return abi_lib()
+
+
+_STRUCT_TOKEN = {'epropnp_problem': 'problem*', 'epropnp_lm_params': 'lm*', 'epropnp_amis_params': 'amis*',
+                 'epropnp_mc_params': 'mc*', 'epropnp_diag': 'diag*'}
+_SCALAR_TOKEN = {'int': 'i', 'int32_t': 'i', 'int64_t': 'l', 'uint64_t': 'u', 'size_t': 'z', 'float': 'f', 'double': 'd'}
+_POINTEES = ('void', 'float', 'double', 'int8_t', 'uint8_t', 'int32_t', 'int64_t', 'uint64_t')
+
+
+def _c_type_token(decl, is_parameter):
+    """One C declaration of the header ('const float* pose_init', 'uint64_t') -> its token in _hip.SIGNATURES; `int32_t*` -> 'i*',
+    which a plain 'p' of the table also covers.  ValueError for anything else."""
+    words = [w for w in decl.replace('*', ' * ').split() if w != 'const']
+    if is_parameter and len(words) > 1 and words[-1] != '*':
+        words = words[:-1]      # the parameter's name
+    if len(words) == 1 and words[0] in _SCALAR_TOKEN:
+        return _SCALAR_TOKEN[words[0]]
+    if len(words) == 2 and words[1] == '*':
+        if words[0] in _STRUCT_TOKEN:
+            return _STRUCT_TOKEN[words[0]]
+        if words[0] == 'char':
+            return 's'
+        if words[0] in _POINTEES:
+            return 'i*' if words[0] == 'int32_t' else 'p'
+    raise ValueError(f'cannot classify {decl!r}')
+
+
+def header_signatures():
+    """{function: (return token, [parameter tokens])} of every prototype in include/epropnp_hip.h.  Whatever is left of the header
+    after comments, preprocessor lines, struct typedefs and the extern "C" braces must read as a prototype: ValueError otherwise."""
+    txt = open(os.path.join(ROOT, 'include', 'epropnp_hip.h')).read()
+    txt = re.sub(r'/\*.*?\*/', ' ', txt, flags=re.S)
+    txt = re.sub(r'^\s*#.*$', '', txt, flags=re.M)
+    txt = re.sub(r'typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;', '', txt, flags=re.S)
+    txt = re.sub(r'extern\s+"C"\s*\{|^\s*\}\s*$', '', txt, flags=re.M)
+    out = {}
+    for stmt in filter(None, (s.strip() for s in txt.split(';'))):
+        m = re.fullmatch(r'([\w\s\*]+?)\s*\b(epropnp_\w+)\s*\(([^()]*)\)', stmt)
+        if m is None:
+            raise ValueError(f'cannot read {stmt!r} as a prototype')
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ('', 'void') else params.split(',')
+        assert name not in out, f'{name} declared twice'
+        out[name] = (_c_type_token(ret, False), [_c_type_token(p, True) for p in params])
+    return out
+
+
+def signature_mismatches(table, header):
+    """What differs between a signature table in the form of _hip.SIGNATURES and header_signatures(), one line per difference."""
+    from epropnp import _hip
+    same = lambda mine, theirs: mine == theirs or (mine == 'p' and theirs == 'i*')
+    bad = [f'{name}: in the table, not in the header' for name in table if name not in header]
+    for name, (ret, params) in header.items():
+        if name not in table:
+            bad.append(f'{name}: in the header, not in the table')
+            continue
+        my_ret, my_params = _hip.signature(name, table)
+        unknown = [t for t in [my_ret] + my_params if t not in _hip.CTYPES]
+        if unknown:
+            bad.append(f'{name}: unknown token(s) {unknown}')
+        if not same(my_ret, ret):
+            bad.append(f'{name}: returns {ret}, the table says {my_ret}')
+        if len(my_params) != len(params):
+            bad.append(f'{name}: {len(params)} parameters, the table has {len(my_params)}')
+        bad += [f'{name}: parameter {i} is {theirs}, the table says {mine}'
+                for i, (mine, theirs) in enumerate(zip(my_params, params)) if not same(mine, theirs)]
+    return bad
+
+
+def test_signature_table_matches_the_header():
+    """Every prototype of the header against the binding's table: return type and each parameter's type class, the struct pointers
+    by the struct's name.  The parser reads every prototype (it raises on one it cannot) and finds as many as declared_symbols()."""
+    from epropnp import _hip
+    header = header_signatures()
+    assert sorted(header) == declared_symbols() and len(header) == len(declared_symbols())
+    assert signature_mismatches(_hip.SIGNATURES, header) == []
+    used = {t for name in _hip.SIGNATURES for t in _hip.signature(name)[1]}
+    assert set(_STRUCT_TOKEN.values()) <= used and {'i', 'l', 'u', 'z', 'f', 'd', 's', 'p'} <= used      # every class is exercised
+
+
+def test_signature_check_reports_a_wrong_table():
+    """The comparison can fail: a dropped parameter, an int32_t taken for an int64_t, a struct pointer taken for a plain pointer or
+    for another struct, a wrong return type and a missing or extra function are each reported, naming the function."""
+    from epropnp import _hip
+    header = header_signatures()
+
+    def mutated(name, edit):
+        ret, params = _hip.signature(name)
+        ret, params = edit(ret, list(params))
+        return dict(_hip.SIGNATURES, **{name: f'{ret}: {" ".join(params)}'})
+    cases = {
+        'epropnp_lm_solve': lambda r, p: (r, p[:-1]),                                          # one parameter dropped
+        'epropnp_weight_stats': lambda r, p: (r, [p[0], 'l'] + p[2:]),                         # int32_t -> int64_t
+        'epropnp_evaluate_cost': lambda r, p: (r, ['p'] + p[1:]),                              # struct pointer -> plain pointer
+        'epropnp_rslm_solve': lambda r, p: (r, [p[0], 'amis*'] + p[2:]),                       # the wrong struct
+        'epropnp_exchange_pack': lambda r, p: (r, [p[0], 'z'] + p[2:]),                        # uint64_t -> size_t
+        'epropnp_bev_nms_scratch_bytes': lambda r, p: ('u', p),                                # size_t -> uint64_t return
+        'epropnp_async_status_word': lambda r, p: ('i', p),                                    # pointer return -> int
+    }
+    for name, edit in cases.items():
+        assert _hip.signature(name, mutated(name, edit)) != _hip.signature(name), name        # (the edit changed something)
+        bad = signature_mismatches(mutated(name, edit), header)
+        assert len(bad) == 1 and bad[0].startswith(name + ':'), (name, bad)
+    less = {k: v for k, v in _hip.SIGNATURES.items() if k != 'epropnp_noise_stride'}
+    assert signature_mismatches(less, header) == ['epropnp_noise_stride: in the header, not in the table']
+    more = dict(_hip.SIGNATURES, epropnp_no_such_entry='i: p')
+    assert signature_mismatches(more, header) == ['epropnp_no_such_entry: in the table, not in the header']
+    with pytest.raises(ValueError, match='cannot classify'):
+        _c_type_token('long double x', True)
+
+
+def test_every_function_of_the_loaded_library_is_typed(lib):
+    """The loader gives every exported function argtypes and restype from the table, the four without parameters included."""
+    from epropnp import _hip
+    for name in _hip.EXPORTS:
+        ret, params = _hip.signature(name)
+        fn = getattr(lib, name)
+        assert fn.restype is _hip.CTYPES[ret] and list(fn.argtypes) == [_hip.CTYPES[t] for t in params], name
+    assert lib.epropnp_async_status_word.restype is ctypes.POINTER(ctypes.c_int32)
 
 
 def test_exports_match_header(lib):
@@ -44,7 +155,6 @@ def test_abi_version_and_noise_stride(lib):
 
 def test_argument_validation_without_launch(lib):
     from epropnp import _hip
-    lib.epropnp_last_error.restype = ctypes.c_char_p
     prob = _hip.Problem(None, None, None, None, None, None, None, 0.1, 4, 16, 5)
     rc = lib.epropnp_evaluate_cost(ctypes.byref(prob), None, 1, None, None)
     assert rc == -1 and b'dof' in lib.epropnp_last_error()

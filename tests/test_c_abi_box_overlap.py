@@ -3,14 +3,12 @@ the header is still plain C, the entries validate their arguments on the host, n
 counts follow no pointer, the plan's tile table is what the header says, a table entry that points outside the boxes or the output is
 skipped on the device, and both launches show up in the stage recorder."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
+
 NEW = ('epropnp_box_overlap', 'epropnp_box_overlap_plan', 'epropnp_box_overlap_segmented')
 EINVAL = -1
 BEV, BOX3D, IMAGE = 0, 1, 2
@@ -21,44 +19,19 @@ COUNTS_A, COUNTS_B = [0, 3, 70, 1, 0, 64], [5, 0, 65, 1, 0, 130]
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    handle = ctypes.CDLL(LIB)
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    handle.epropnp_last_error.restype = ctypes.c_char_p
-    handle.epropnp_box_overlap.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp]
-    handle.epropnp_box_overlap_plan.argtypes = [vp, vp, i32, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
-    handle.epropnp_box_overlap_segmented.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, i32, vp, i32, vp, i64, vp]
-    return handle
+    return abi_lib()
 
 
 def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    for name in NEW:
-        assert hasattr(lib, name), f'{name} not exported'
-        assert name in _hip.EXPORTS
+    check_abi_additive(lib, NEW)
 
 
 def test_header_with_the_box_overlap_entries_is_plain_c(tmp_path):
-    src = tmp_path / 'box_overlap.c'
-    src.write_text('#include <stdio.h>\n#include "epropnp_hip.h"\nint main(void) {\n'
-                   f'  printf("%d %d %d\\n", (int)(sizeof(&{NEW[0]}) > 0), (int)(sizeof(&{NEW[1]}) > 0), (int)(sizeof(&{NEW[2]}) > 0));\n'
-                   f'  return (EPROPNP_BOX_BEV == {BEV} && EPROPNP_BOX_3D == {BOX3D} && EPROPNP_BOX_IMAGE == {IMAGE} &&\n'
-                   f'          EPROPNP_BOX_CRIT_IOU == {IOU} && EPROPNP_BOX_CRIT_A == {CRIT_A} && EPROPNP_BOX_CRIT_B == {CRIT_B} &&\n'
-                   f'          EPROPNP_BOX_CRIT_INTER == {INTER} && EPROPNP_BOX_HEIGHT_INTERVAL == {INTERVAL} &&\n'
-                   f'          EPROPNP_BOX_HEIGHT_REFERENCE_TORCH == {REFERENCE_TORCH} && EPROPNP_BOX_TILE_INTS == 6) ? 0 : 1;\n}}\n')
-    inc = os.path.join(ROOT, 'include')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', inc, '-fsyntax-only', str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    exe = tmp_path / 'box_overlap'
-    r = subprocess.run(['gcc', '-std=c99', '-pedantic', '-Werror', '-I', inc, '-c', str(src), '-o', str(exe) + '.o'], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c(tmp_path, NEW, run=True, facts=[
+        f'EPROPNP_BOX_BEV == {BEV}', f'EPROPNP_BOX_3D == {BOX3D}', f'EPROPNP_BOX_IMAGE == {IMAGE}', f'EPROPNP_BOX_CRIT_IOU == {IOU}',
+        f'EPROPNP_BOX_CRIT_A == {CRIT_A}', f'EPROPNP_BOX_CRIT_B == {CRIT_B}', f'EPROPNP_BOX_CRIT_INTER == {INTER}',
+        f'EPROPNP_BOX_HEIGHT_INTERVAL == {INTERVAL}', f'EPROPNP_BOX_HEIGHT_REFERENCE_TORCH == {REFERENCE_TORCH}',
+        'EPROPNP_BOX_TILE_INTS == 6'])
 
 
 def test_no_boxes_is_not_an_error_and_touches_no_pointer(lib):

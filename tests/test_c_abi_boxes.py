@@ -1,55 +1,28 @@
 """epropnp_bev_overlap / epropnp_bev_nms / epropnp_bev_nms_scratch_bytes are additive entries of the C ABI: same ABI version, the
 header is still plain C, the entries validate their arguments on the host, naming themselves, before anything is launched, an
 `order` entry outside [0, N) is skipped on the device, and both calls show up in the stage recorder."""
-import ctypes
-import os
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
+
 NEW = ('epropnp_bev_overlap', 'epropnp_bev_nms', 'epropnp_bev_nms_scratch_bytes')
 EINVAL = -1
 
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    handle = ctypes.CDLL(LIB)
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    handle.epropnp_last_error.restype = ctypes.c_char_p
-    handle.epropnp_bev_overlap.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
-    handle.epropnp_bev_nms.argtypes = [vp, vp, vp, i32, ctypes.c_float, vp, ctypes.c_size_t, vp, vp, vp, vp]
-    handle.epropnp_bev_nms_scratch_bytes.argtypes = [i32]
-    handle.epropnp_bev_nms_scratch_bytes.restype = ctypes.c_size_t
-    return handle
+    return abi_lib()
 
 
 def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    for name in NEW:
-        assert hasattr(lib, name), f'{name} not exported'
-        assert name in _hip.EXPORTS
+    check_abi_additive(lib, NEW)
 
 
 def test_header_with_the_box_entries_is_plain_c(tmp_path):
     from epropnp import boxes
-    src = tmp_path / 'boxes.c'
-    src.write_text('#include <stdio.h>\n#include "epropnp_hip.h"\nint main(void) {\n'
-                   f'  printf("%d %d %d\\n", (int)(sizeof(&{NEW[0]}) > 0), (int)(sizeof(&{NEW[1]}) > 0), (int)(sizeof(&{NEW[2]}) > 0));\n'
-                   f'  return EPROPNP_BEV_TILE == {boxes.TILE} ? 0 : 1;\n}}\n')
-    inc = os.path.join(ROOT, 'include')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', inc, '-fsyntax-only', str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c(tmp_path, NEW, facts=[f'EPROPNP_BEV_TILE == {boxes.TILE}'])
 
 
 def test_no_boxes_is_not_an_error_and_touches_no_pointer(lib):

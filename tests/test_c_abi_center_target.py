@@ -1,54 +1,28 @@
 """epropnp_volume_centers / epropnp_box_thickness and the scratch size query are additive entries of the C ABI: same ABI version, the
 header is still plain C, the entries validate their arguments on the host, naming themselves, before anything is launched, zero
 objects follow no pointer, and a call through raw pointers gives the bits of the Python path."""
-import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
+
 NEW = ('epropnp_volume_centers', 'epropnp_box_thickness', 'epropnp_volume_centers_scratch_bytes')
 EINVAL = -1
 
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    handle = ctypes.CDLL(LIB)
-    vp, i32, f32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_size_t
-    handle.epropnp_last_error.restype = ctypes.c_char_p
-    handle.epropnp_volume_centers.argtypes = [vp] * 6 + [i32] * 9 + [f32, f32, i32, vp, sz, vp, vp, vp, vp]
-    handle.epropnp_box_thickness.argtypes = [vp] * 3 + [i32] * 6 + [f32, vp, sz, vp, vp, vp]
-    handle.epropnp_volume_centers_scratch_bytes.argtypes = [i32, i32, i32]
-    handle.epropnp_volume_centers_scratch_bytes.restype = sz
-    return handle
+    return abi_lib()
 
 
 def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    for name in NEW:
-        assert hasattr(lib, name), f'{name} not exported'
-        assert name in _hip.EXPORTS
+    check_abi_additive(lib, NEW)
 
 
 def test_header_with_the_centre_target_entries_is_plain_c(tmp_path):
-    src = tmp_path / 'center_target.c'
-    src.write_text('#include <stdio.h>\n#include "epropnp_hip.h"\nint main(void) {\n'
-                   + ''.join(f'  printf("%d\\n", (int)(sizeof(&{n}) > 0));\n' for n in NEW)
-                   + '  return EPROPNP_ABI_VERSION == 7 ? 0 : 1;\n}\n')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', os.path.join(ROOT, 'include'),
-                        '-fsyntax-only', str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c(tmp_path, NEW)
 
 
 def test_scratch_query(lib):

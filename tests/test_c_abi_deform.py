@@ -1,47 +1,27 @@
 """epropnp_deform_sample_forward / epropnp_deform_sample_backward are additive entries of the C ABI: same ABI version, the header is
 still plain C, and one forward / backward through raw pointers with a strided (channels-last) key gives the bits of the Python path
 (dkey / dvalue, float-atomic sums, to rounding)."""
-import ctypes
-import os
-import subprocess
 
 import pytest
 import torch
 
 import test_deform as td
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
 NEW = ('epropnp_deform_sample_forward', 'epropnp_deform_sample_backward')
 
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    return ctypes.CDLL(LIB)
+    return abi_lib()
 
 
 def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    for name in NEW:
-        assert hasattr(lib, name), f'{name} not exported'
-        assert name in _hip.EXPORTS
+    check_abi_additive(lib, NEW)
 
 
 def test_header_with_the_deform_entries_is_plain_c(tmp_path):
-    src = tmp_path / 'deform.c'
-    src.write_text('#include <stdio.h>\n#include "epropnp_hip.h"\nint main(void) {\n'
-                   + ''.join(f'  printf("%d\\n", (int)(sizeof(&{n}) > 0));\n' for n in NEW)
-                   + '  return EPROPNP_ABI_VERSION == 7 ? 0 : 1;\n}\n')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', os.path.join(ROOT, 'include'),
-                        '-fsyntax-only', str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c(tmp_path, NEW)
 
 
 def test_raw_pointer_calls_match_the_python_path(backend):

@@ -1,54 +1,27 @@
 """epropnp_orient_density / epropnp_bev_density and their scratch size queries are additive entries of the C ABI: same ABI version,
 the header is still plain C, the entries validate their arguments on the host, naming themselves, before anything is launched, zero
 counts follow no pointer, and a call through raw pointers gives the bits of the Python path."""
-import ctypes
-import os
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
+
 NEW = ('epropnp_orient_density', 'epropnp_bev_density', 'epropnp_orient_density_scratch_bytes', 'epropnp_bev_density_scratch_bytes')
 EINVAL = -1
 
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    handle = ctypes.CDLL(LIB)
-    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    handle.epropnp_last_error.restype = ctypes.c_char_p
-    handle.epropnp_orient_density.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, ctypes.c_size_t, vp, vp, vp, vp, vp]
-    handle.epropnp_bev_density.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, ctypes.c_size_t, vp, vp, vp]
-    for name in NEW[2:]:
-        getattr(handle, name).argtypes = [i32, i32]
-        getattr(handle, name).restype = ctypes.c_size_t
-    return handle
+    return abi_lib()
 
 
 def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    for name in NEW:
-        assert hasattr(lib, name), f'{name} not exported'
-        assert name in _hip.EXPORTS
+    check_abi_additive(lib, NEW)
 
 
 def test_header_with_the_density_entries_is_plain_c(tmp_path):
-    src = tmp_path / 'density.c'
-    src.write_text('#include <stdio.h>\n#include "epropnp_hip.h"\nint main(void) {\n'
-                   + ''.join(f'  printf("%d\\n", (int)(sizeof(&{n}) > 0));\n' for n in NEW)
-                   + '  return EPROPNP_ABI_VERSION == 7 ? 0 : 1;\n}\n')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', os.path.join(ROOT, 'include'),
-                        '-fsyntax-only', str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c(tmp_path, NEW)
 
 
 def test_scratch_queries(lib):

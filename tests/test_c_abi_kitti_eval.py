@@ -2,15 +2,12 @@
 the C ABI: same ABI version, the header is still plain C, the entries validate their arguments on the host, naming themselves, before
 anything is launched, zero cases follow no pointer, a direct call gives what the header says, and offsets that point outside the arrays
 -- device memory, which the host cannot check -- make the kernels skip that image."""
-import ctypes
-import os
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
+
 NEW = ('epropnp_kitti_match', 'epropnp_kitti_thresholds', 'epropnp_kitti_statistics', 'epropnp_kitti_match_scratch_bytes',
        'epropnp_kitti_statistics_scratch_bytes')
 EINVAL = -1
@@ -22,45 +19,17 @@ STATS = ['ov', 'f64', 'nov', 'go', 'do', 'qo', 'blk', 'I', 'gt', 'dt', 'dc', 'G'
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    handle = ctypes.CDLL(LIB)
-    vp, i32, i64, f64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_size_t
-    handle.epropnp_last_error.restype = ctypes.c_char_p
-    handle.epropnp_kitti_match.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp]
-    handle.epropnp_kitti_thresholds.argtypes = [vp, vp, vp, i32, i32, f64, vp, vp, vp]
-    handle.epropnp_kitti_statistics.argtypes = [vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32,
-                                                i32, vp, sz, vp, vp, vp]
-    handle.epropnp_kitti_match_scratch_bytes.argtypes = [i32, i32]
-    handle.epropnp_kitti_match_scratch_bytes.restype = sz
-    handle.epropnp_kitti_statistics_scratch_bytes.argtypes = [i32, i32, i32, i32]
-    handle.epropnp_kitti_statistics_scratch_bytes.restype = sz
-    return handle
+    return abi_lib()
 
 
 def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    for name in NEW:
-        assert hasattr(lib, name), f'{name} not exported'
-        assert name in _hip.EXPORTS
+    check_abi_additive(lib, NEW)
 
 
 def test_header_with_the_kitti_entries_is_plain_c(tmp_path):
-    src = tmp_path / 'kitti_eval.c'
-    uses = ' + '.join(f'(int)(sizeof(&{n}) > 0)' for n in NEW)
-    src.write_text('#include <stdio.h>\n#include "epropnp_hip.h"\nint main(void) {\n'
-                   f'  printf("%d\\n", {uses});\n'
-                   '  return (EPROPNP_KITTI_SAMPLE_PTS == 41 && EPROPNP_KITTI_GT_SKIPPED == -1 && EPROPNP_KITTI_GT_UNMATCHED == 0 &&\n'
-                   '          EPROPNP_KITTI_GT_TRUE_POSITIVE == 1 && EPROPNP_KITTI_GT_MISSED == 2 && EPROPNP_KITTI_GT_IGNORED_MATCH == 3) ? 0 : 1;\n}\n')
-    inc = os.path.join(ROOT, 'include')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', inc, '-fsyntax-only', str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c(tmp_path, NEW, facts=[
+        'EPROPNP_KITTI_SAMPLE_PTS == 41', 'EPROPNP_KITTI_GT_SKIPPED == -1', 'EPROPNP_KITTI_GT_UNMATCHED == 0',
+        'EPROPNP_KITTI_GT_TRUE_POSITIVE == 1', 'EPROPNP_KITTI_GT_MISSED == 2', 'EPROPNP_KITTI_GT_IGNORED_MATCH == 3'])
 
 
 def test_scratch_size_queries(lib):

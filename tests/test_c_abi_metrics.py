@@ -1,51 +1,26 @@
 """epropnp_pose_errors / epropnp_pose_errors_scratch_bytes are additive entries of the C ABI: same ABI version, the header is still
 plain C, and the entry validates its arguments on the host, naming itself, before anything is launched."""
-import ctypes
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
+
 NEW = ('epropnp_pose_errors', 'epropnp_pose_errors_scratch_bytes')
 EINVAL = -1
 
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    handle = ctypes.CDLL(LIB)
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    handle.epropnp_last_error.restype = ctypes.c_char_p
-    handle.epropnp_pose_errors.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp]
-    handle.epropnp_pose_errors_scratch_bytes.argtypes = [i32, i32, i32]
-    handle.epropnp_pose_errors_scratch_bytes.restype = ctypes.c_size_t
-    return handle
+    return abi_lib()
 
 
 def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    for name in NEW:
-        assert hasattr(lib, name), f'{name} not exported'
-        assert name in _hip.EXPORTS
+    check_abi_additive(lib, NEW)
 
 
 def test_header_with_the_metrics_entries_is_plain_c(tmp_path):
-    src = tmp_path / 'metrics.c'
-    src.write_text('#include <stdio.h>\n#include "epropnp_hip.h"\nint main(void) {\n'
-                   f'  printf("%d %d\\n", (int)(sizeof(&{NEW[0]}) > 0), (int)(sizeof(&{NEW[1]}) > 0));\n'
-                   '  return EPROPNP_POSE_ERROR_WORDS == 8 && EPROPNP_POSE_ERROR_QUERY_TILE > 0 && EPROPNP_POSE_ERROR_CAND_TILE > 0 ? 0 : 1;\n}\n')
-    inc = os.path.join(ROOT, 'include')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', inc, '-fsyntax-only', str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c(tmp_path, NEW, facts=['EPROPNP_POSE_ERROR_WORDS == 8', 'EPROPNP_POSE_ERROR_QUERY_TILE > 0',
+                                                  'EPROPNP_POSE_ERROR_CAND_TILE > 0'])
 
 
 def test_no_objects_is_not_an_error_and_touches_no_pointer(lib):

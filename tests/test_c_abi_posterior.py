@@ -1,63 +1,26 @@
 """The posterior additions to the C ABI (epropnp_posterior_summary, epropnp_posterior_resample) are additive: same ABI version, the
 header is still plain C, and both entries validate their arguments on the host, naming themselves, before anything is launched."""
-import ctypes
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
+
 NEW = ('epropnp_posterior_summary', 'epropnp_posterior_resample')
 EINVAL = -1
 
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    handle = ctypes.CDLL(LIB)
-    vp, i32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64
-    handle.epropnp_last_error.restype = ctypes.c_char_p
-    handle.epropnp_posterior_summary.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
-    handle.epropnp_posterior_resample.argtypes = [vp, vp, i32, i32, i32, i32, vp, u64, u64, vp, vp, vp]
-    return handle
+    return abi_lib()
 
 
 def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    for s in NEW:
-        assert hasattr(lib, s), f'{s} not exported'
-        assert s in _hip.EXPORTS
+    check_abi_additive(lib, NEW)
 
 
 def test_header_with_the_posterior_entries_is_plain_c(tmp_path):
-    if shutil.which('gcc') is None:
-        pytest.skip('gcc not available')
-    lines = ['#include <stdio.h>', '#include "epropnp_hip.h"', 'int main(void) {',
-             '  printf("words %d\\n", EPROPNP_POSTERIOR_WORDS);']
-    lines += [f'  printf("{s} %d\\n", (int)(sizeof(&{s}) > 0));' for s in NEW] + ['  return 0;', '}']      # (the symbols must link)
-    src = tmp_path / 'posterior.c'
-    src.write_text('\n'.join(lines) + '\n')
-    inc = os.path.join(ROOT, 'include')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', inc, '-fsyntax-only', str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    exe = tmp_path / 'posterior'
-    libdir = os.path.dirname(LIB)
-    r = subprocess.run(['gcc', '-std=c99', '-I', inc, str(src), '-o', str(exe), '-L', libdir, '-lepropnp_hip',
-                        '-Wl,-rpath,' + libdir, '-Wl,-rpath,/opt/rocm/lib', '-L', '/opt/rocm/lib'], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stderr
-    got = dict(line.split() for line in out.stdout.splitlines())
-    assert got['words'] == '16' and all(got[s] == '1' for s in NEW)
+    got = check_header_is_plain_c(tmp_path, NEW, run=True, body=['printf("words %d\\n", EPROPNP_POSTERIOR_WORDS);'])
+    assert got['words'] == '16'
 
 
 def test_no_objects_is_not_an_error_and_touches_no_pointer(lib):

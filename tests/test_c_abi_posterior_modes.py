@@ -1,47 +1,25 @@
 """epropnp_posterior_modes is an additive entry of the C ABI: same ABI version, the header is still plain C, and the entry validates
 its arguments on the host, naming itself, before anything is launched."""
-import ctypes
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'epro-pnp_amd', 'lib', 'libepropnp_hip.so')
+from helpers import abi_lib, check_abi_additive, check_header_is_plain_c
+
 NEW = 'epropnp_posterior_modes'
 EINVAL = -1
 
 
 @pytest.fixture(scope='module')
 def lib():
-    if not os.path.exists(LIB):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('epropnp_build', os.path.join(ROOT, 'epro-pnp_amd', 'build.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    handle = ctypes.CDLL(LIB)
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    handle.epropnp_last_error.restype = ctypes.c_char_p
-    handle.epropnp_posterior_modes.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    return handle
+    return abi_lib()
 
 
 def test_new_symbol_is_exported_and_the_abi_version_stays(lib):
-    from epropnp import _hip
-    assert lib.epropnp_abi_version() == 7 and _hip.ABI_VERSION == 7
-    assert hasattr(lib, NEW), f'{NEW} not exported'
-    assert NEW in _hip.EXPORTS
+    check_abi_additive(lib, [NEW])
 
 
 def test_header_with_the_modes_entry_is_plain_c(tmp_path):
-    src = tmp_path / 'modes.c'
-    src.write_text('#include <stdio.h>\n#include "epropnp_hip.h"\nint main(void) {\n'
-                   f'  printf("{NEW} %d\\n", (int)(sizeof(&{NEW}) > 0));\n  return 0;\n}}\n')
-    inc = os.path.join(ROOT, 'include')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I', inc, '-fsyntax-only', str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c(tmp_path, [NEW])
 
 
 def test_no_objects_is_not_an_error_and_touches_no_pointer(lib):
